@@ -17,12 +17,18 @@
   visible GPUs than N, is an error — never a silent 1-GPU run.  `--dry-run` walks launcher / sharding / gather / JSON on
   CPU (gloo) and measures nothing.
 
-  OUTPUT.  Rank 0 prints TWO lines: first `bench_detail: {...}` — everything measured, also written to
-  gpurun_out/bench_detail.json — and LAST the contract line: one JSON object of at most 4 KB (contract_line(): the
+  A PLAIN run (`--gpus N --steps K --warmup W`) does what the headline needs and nothing else: set-up, settle + warm-up,
+  the K timed steps, the outputs of the last step if `--dump-outputs DIR` is given (DIR/<name>.npy, float32, <= 64 MB:
+  image 0 whole and a seeded sample of pixels over every image), and the contract line.  `--full` adds everything
+  else: the sustained repeat, the oracle spot check (`verified_vs_oracle`), the gather (N > 1) and the side legs.
+
+  OUTPUT.  With --full, rank 0 prints TWO lines: first `bench_detail: {...}` — everything measured, also
+  written to the --detail file — and LAST the contract line: one JSON object of at most 4 KB (contract_line(): the
   headline, `roofline`, `cpu_baseline`, and ten scalars of the side legs as `e2e_summary`).  The side legs themselves
   (kernel-only figure at 4,096 images, the N > 1 job on one GPU, arithmetic classes, JPEG bytes -> RGB through
   jpgpu_pipeline_decode incl. BASELINE configs[3], the CPU-budget points, the oracle's whole decode) are
-  tools/bench_e2e.py; each is checked against the oracle and none of them is inside `value`."""
+  tools/bench_e2e.py; each is checked against the oracle and none of them is inside `value`.  A plain run prints the
+  contract line alone."""
 import argparse
 import hashlib
 import json
@@ -89,7 +95,13 @@ def parse_args(argv=None):
     ap.add_argument("--settle", type=int, default=-1,
                     help="untimed launches BEFORE the warm-up steps (the GPU leaves its clock transient after an idle period); "
                          "default: enough to make settle + warm-up = 50 launches at N = 1")
-    ap.add_argument("--detail", default=DETAIL_PATH, help="where the detail document goes (also printed as the `bench_detail:` line)")
+    ap.add_argument("--detail", default=None,
+                    help="where the detail document goes (also printed as the `bench_detail:` line); with --full it defaults to DETAIL_PATH")
+    ap.add_argument("--full", action="store_true",
+                    help="everything besides the headline: the sustained repeat, the oracle check, the gather (N > 1), the per-class and "
+                         "torch.add figures, k_4096, scale_anchor, the e2e legs and the CPU baselines, and the detail document")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps, write what the last step computed as DIR/<name>.npy (float32, at most 64 MB in all)")
     return ap.parse_args(argv)
 
 
@@ -213,6 +225,44 @@ def measured_traffic(workload, path):
     return None, "not measured for this workload / kernel path", None
 
 
+DUMP_BYTES_MAX = 64 << 20  # --dump-outputs: every file of one run together
+DUMP_SEED = 0x5EED
+
+
+def dump_outputs(shard, n_img, w, h, out_dir, rank=0, world=1):
+    """The pixels of the last timed step as float32 .npy files: image 0 whole (H x W x C) where it fits half the budget, and a seeded
+    sample of pixel bytes over every image of the shard (the same positions for the same arguments).  Returns {name: shape}."""
+    import torch
+    budget = DUMP_BYTES_MAX // max(world, 1) - 4096  # (room for the .npy headers)
+    prefix = f"rank{rank}_" if world > 1 else ""
+    offs, sizes = [], []
+    for s, (a, b) in enumerate(shard.bounds):
+        bt = shard.batches[s]
+        for i in range(a, b):
+            offs.append(shard.out_base[s] + bt.out_offset(i - a))
+            sizes.append(bt.out_bytes(i - a))
+    offs, sizes = np.array(offs[:n_img], dtype=np.int64), np.array(sizes[:n_img], dtype=np.int64)
+    os.makedirs(out_dir, exist_ok=True)
+    wrote = {}
+    img0 = shard.image_pixels(0)
+    if img0.numel() * 4 <= budget // 2:
+        a = img0.cpu().numpy().astype(np.float32)
+        if a.size % (w * h) == 0:
+            a = a.reshape(h, w, a.size // (w * h))
+        np.save(os.path.join(out_dir, prefix + "pixels_image0.npy"), a)
+        wrote[prefix + "pixels_image0"] = a.shape
+        budget -= a.nbytes
+    n = int(min(int(sizes.sum()), budget // 4, 1 << 22))
+    rng = np.random.default_rng(DUMP_SEED)
+    img = rng.integers(0, len(sizes), n)
+    idx = offs[img] + np.minimum((rng.random(n) * sizes[img]).astype(np.int64), sizes[img] - 1)
+    assert n == 0 or (idx.min() >= 0 and idx.max() < shard.out_arena.numel()), "sample outside the pixel arena"
+    a = shard.out_arena[torch.from_numpy(idx).to(shard.out_arena.device)].cpu().numpy().astype(np.float32)
+    np.save(os.path.join(out_dir, prefix + "pixels_sample.npy"), a)
+    wrote[prefix + "pixels_sample"] = a.shape
+    return wrote
+
+
 def time_steps(torch, dev, dist, stream, steps, body):
     """`steps` calls of body() between barrier + synchronize on both sides; (wall seconds, GPU ms per step from events
     on the stream the kernels are launched on)."""
@@ -327,13 +377,18 @@ def contract_line(detail, detail_path=None):
     return txt
 
 
-def emit(detail, detail_path):
-    """Rank 0: the detail document (file + an earlier stdout line), then — LAST — the contract line."""
+def flush_c_stdio():
+    """Write out what sits in the C library's stdout buffer (the collective library's banner) before a line of ours that must be last."""
     try:
         import ctypes
-        ctypes.CDLL(None).fflush(None)  # (the collective library's banner sits in the C library's stdout buffer: out with it first)
+        ctypes.CDLL(None).fflush(None)
     except OSError:
         pass
+
+
+def emit(detail, detail_path):
+    """Rank 0: the detail document (file + an earlier stdout line), then — LAST — the contract line."""
+    flush_c_stdio()
     where = None
     if detail_path:
         try:
@@ -434,13 +489,19 @@ def main(argv=None):
     elapsed, gpu_ms_per_step = time_steps(torch, dev, dist, stream, steps, lambda: shard.decode(stream))
     if dist:
         elapsed, gpu_ms_per_step = D.max_over_ranks([elapsed, gpu_ms_per_step], device=dev)
+    leg("headline", t0)
+    if args.dump_outputs:
+        t0 = time.perf_counter()
+        dump_outputs(shard, n_img, w, h, args.dump_outputs, rank, world)
+        leg("dump_outputs", t0)
+    t0 = time.perf_counter()
     n_ranks_seen = None
     if dist:  # the record proves how many ranks the collective library saw (a sum of ones over all ranks)
         ones = torch.ones(1, dtype=torch.int32, device=dev)
         dist.all_reduce(ones)
         n_ranks_seen = int(ones.item())
     sustained = None
-    if args.min_seconds > 0:
+    if args.full and args.min_seconds > 0:
         # The same step, repeated for at least --min-seconds (in chunks of the K steps timed above): an independent look at
         # `value` that lasts long enough for an outside sampler of GPU activity to see the device busy.
         s_steps, s_elapsed = 0, 0.0
@@ -453,11 +514,11 @@ def main(argv=None):
             s_elapsed += e
             chunk = min(chunk * 2, max(steps, int(chunk * args.min_seconds / max(e, 1e-6)) + 1))
         sustained = (s_steps, s_elapsed)
-    leg("headline", t0)
+        leg("sustained", t0)
 
     # parity spot check inside the bench (oracle = checker only, never the thing measured)
     verified, digest, O = None, None, None
-    if rank == 0:
+    if rank == 0 and args.full:
         t0 = time.perf_counter()
         import oracle as O
         verified = True
@@ -508,8 +569,9 @@ def main(argv=None):
                          "traffic": traffic, "traffic_source": traffic_source, **(traffic_prov or {}),
                          "algorithmic_bytes_per_launch": alg_bytes, "kernel_ms_per_launch": round(gpu_ms_per_step, 4),
                          "launch": "one step of this rank's shard" + (f" = {len(shard.batches)} launch groups" if len(shard.batches) > 1 else "")},
-            "verified_vs_oracle": verified,
         }
+        if args.full:
+            line["verified_vs_oracle"] = verified
         if sustained:
             line["sustained"] = {"steps": sustained[0], "seconds": round(sustained[1], 3),
                                  "value": round(mp_per_step * sustained[0] / sustained[1], 1), "unit": "MP/s",
@@ -523,7 +585,7 @@ def main(argv=None):
         line["config"]["arena_fill_copies"] = shard.fill_copies
 
     # ---- N > 1: the same job with the final gather inside the timed region, overlapped per launch group ----
-    if dist and not args.no_gather:
+    if dist and args.full and not args.no_gather:
         # (never lose the bench line to the collective: whatever goes wrong in here is reported in the line instead)
         t0 = time.perf_counter()
         gather_error = None
@@ -568,7 +630,7 @@ def main(argv=None):
         leg("gather", t0)
 
     # ---- N = 1 side legs (tools/bench_e2e.py); none of them is inside `value` ----
-    if rank == 0 and world == 1 and not args.no_classes:
+    if rank == 0 and world == 1 and args.full and not args.no_classes:
         t0 = time.perf_counter()
         if not args.generic:
             line["roofline_by_class"] = E.class_sweep(torch, shard, variants, dev, stream, alg_bytes, digest, n_img, args.class_steps)
@@ -593,14 +655,14 @@ def main(argv=None):
         leg(key, t0)
         torch.cuda.empty_cache()
 
-    default_run = world == 1 and workload == "1080p-420" and not args.generic
+    default_run = args.full and world == 1 and workload == "1080p-420" and not args.generic
     if rank == 0 and default_run and not args.no_k4096:
         drop_shard()  # north_star's literal batch: 4096 images on one GPU (51 GB of arenas), same kernels, same verification
         guarded("k_4096", lambda: E.k_4096(J, torch, O, variants, local_rank, dev, stream, w, h, digest))
     if rank == 0 and default_run and not args.no_scale_anchor and not args.force_dist:
         drop_shard()
         guarded("scale_anchor", lambda: E.scale_anchor(J, torch, O, synth, D, local_rank, dev, stream))
-    if dist and not args.no_e2e and not args.generic:
+    if dist and args.full and not args.no_e2e and not args.generic:
         # ---- N > 1 (and --force-dist): E per rank on its shard of the file list, with a per-rank host budget ----
         drop_shard()
         t0 = time.perf_counter()
@@ -631,19 +693,30 @@ def main(argv=None):
                 guarded("cpu_baseline_e2e", lambda: E.cpu_baseline_e2e(O, files, w, h, args.cpu_seconds / 2))
         except Exception as e:  # noqa: BLE001
             line.setdefault("e2e", {})["error"] = f"{type(e).__name__}: {e}"[:300]
-    if rank == 0 and not args.no_cpu_baseline and world == 1 and nv == 1:
+    if rank == 0 and args.full and not args.no_cpu_baseline and world == 1 and nv == 1:
         t0 = time.perf_counter()
         line["cpu_baseline"] = cpu_baseline(O, ocomps, qts, coefs, w, h, ct, args.cpu_seconds)
         leg("cpu_baseline", t0)
     if shard is not None:
         shard.close()
     if dist:
+        flush_c_stdio()  # (every rank: no banner of a peer may come out after rank 0's last line)
         dist.barrier()
         dist.destroy_process_group()
     if rank == 0:
         line["leg_seconds"] = legs
         line["bench_seconds"] = round(time.perf_counter() - t_start, 1)
-        emit(line, args.detail)
+        print_result(line, args.full, args.detail)
+
+
+def print_result(line, full, detail_path):
+    """Rank 0's output: with --full (or --detail) the detail document and then the contract line; a plain run prints the contract
+    line alone.  Either way it is the LAST line on stdout."""
+    if full or detail_path:
+        emit(line, detail_path or DETAIL_PATH)
+    else:
+        flush_c_stdio()
+        print(contract_line(line), flush=True)
 
 
 from bench_e2e import e2e_files, rank_cpu_share  # noqa: E402,F401 (tests reach them through this module)

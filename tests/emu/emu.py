@@ -1,5 +1,6 @@
 """TEST-ONLY: loader for the CPU emulation of the product's device code (tests/emu/*.cpp)."""
 import ctypes as C
+import fcntl
 import os
 import subprocess
 
@@ -10,8 +11,13 @@ _LIB = None
 def lib():
     global _LIB
     if _LIB is None:
-        subprocess.check_call(["make", "-C", _HERE, "-s"])
-        L = C.CDLL(os.path.join(_HERE, "libemu.so"))
+        fd = os.open(_HERE, os.O_RDONLY)  # (pytest workers in parallel: one make at a time, none loads a half-written library)
+        try:
+            fcntl.flock(fd, fcntl.LOCK_EX)
+            subprocess.check_call(["make", "-C", _HERE, "-s"])
+            L = C.CDLL(os.path.join(_HERE, "libemu.so"))
+        finally:
+            os.close(fd)
         L.emu_idct8x8.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]
         L.emu_idct_small.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]
         L.emu_ycbcr.argtypes = [C.c_uint32] * 3

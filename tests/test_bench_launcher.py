@@ -170,3 +170,123 @@ def test_emit_prints_the_detail_first_and_the_contract_line_last(tmp_path, capsy
     last = json.loads(out[-1])
     assert len(out[-1]) < 4096 and last["value"] == detail["value"] and last["detail"] == path
     assert json.load(open(path)) == detail
+
+
+# ---- a plain run and --dump-outputs: the outputs of the last timed step, for comparing two builds output for output ----
+class _FakeBatch:
+    def __init__(self, sizes):
+        self.sizes, self.n_images = sizes, len(sizes)
+
+    def out_offset(self, i):
+        return 64 * i + sum(self.sizes[:i])  # (gaps between images, as an arena may have)
+
+    def out_bytes(self, i):
+        return self.sizes[i]
+
+
+class _FakeShard:
+    """What bench.dump_outputs reads of a Shard, on CPU tensors: two launch groups of 2 x 3-channel 5x4 images."""
+
+    def __init__(self, torch):
+        self.bounds = [(0, 2), (2, 4)]
+        self.batches = [_FakeBatch([60, 60]), _FakeBatch([60, 60])]
+        self.out_base = [0, 512]
+        self.out_arena = torch.full((1024,), 255, dtype=torch.uint8)  # (255 between and after the images: no image byte has it)
+        for i in range(4):
+            self.image_pixels(i)[:] = torch.arange(60, dtype=torch.uint8) + 60 * i  # (image values 0 ... 239)
+
+    def image_pixels(self, i):
+        s = 0 if i < 2 else 1
+        b = self.batches[s]
+        off = self.out_base[s] + b.out_offset(i - self.bounds[s][0])
+        return self.out_arena[off: off + b.out_bytes(i - self.bounds[s][0])]
+
+
+def test_dump_outputs_writes_float32_within_the_cap_and_the_same_every_time(tmp_path):
+    import numpy as np
+    import torch
+    sys.path.insert(0, ROOT)
+    import bench
+    shard = _FakeShard(torch)
+    got = [bench.dump_outputs(shard, 4, 5, 4, str(tmp_path / d)) for d in ("a", "b")]
+    assert got[0] == got[1] == {"pixels_image0": (4, 5, 3), "pixels_sample": (240,)}
+    arena = shard.out_arena.numpy()
+    total = 0
+    for name in got[0]:
+        a, b = np.load(tmp_path / "a" / f"{name}.npy"), np.load(tmp_path / "b" / f"{name}.npy")
+        assert a.dtype == np.float32 and np.array_equal(a, b)
+        total += os.path.getsize(tmp_path / "a" / f"{name}.npy")
+    assert np.array_equal(np.load(tmp_path / "a" / "pixels_image0.npy").reshape(-1), arena[:60].astype(np.float32))
+    sample = np.load(tmp_path / "a" / "pixels_sample.npy")
+    assert (sample < 240).all()  # never a byte between or after the images (255 there)
+    assert len(np.unique(sample)) > 120  # (and spread over the images: 240 draws from 240 values)
+    assert total <= bench.DUMP_BYTES_MAX
+    two = bench.dump_outputs(shard, 4, 5, 4, str(tmp_path / "r"), rank=1, world=2)
+    assert set(two) == {"rank1_pixels_image0", "rank1_pixels_sample"}
+
+
+@pytest.mark.parametrize("full", [False, True])
+def test_result_line_is_last_after_a_banner_in_the_c_stdio_buffer(full, tmp_path):
+    """The collective library writes its banner through C stdio; on a pipe that buffer goes out at process exit, after Python's own
+    lines, unless it is flushed first.  The contract line must stay the LAST stdout line in a plain run and with --full."""
+    script = tmp_path / "emit.py"
+    script.write_text(
+        "import ctypes, json, sys\n"
+        f"sys.path.insert(0, {ROOT!r})\n"
+        "import bench\n"
+        f"detail = json.load(open({os.path.join(ROOT, 'profiles', 'round5', '07_bench_driver_command_final.json')!r}))\n"
+        "ctypes.CDLL(None).printf(b'RCCL version : banner\\n')\n"
+        f"bench.print_result(detail, {full}, {str(tmp_path / 'd.json')!r} if {full} else None)\n")
+    r = subprocess.run([sys.executable, str(script)], capture_output=True, text=True, timeout=120)
+    assert r.returncode == 0, r.stderr[-2000:]
+    lines = r.stdout.strip().splitlines()
+    assert "RCCL version : banner" in lines[:-1], r.stdout[-500:]
+    last = json.loads(lines[-1])
+    assert "value" in last and "ms_per_step" in last
+    assert any(l.startswith("bench_detail:") for l in lines) == full
+
+
+def test_plain_and_full_options_parse():
+    sys.path.insert(0, ROOT)
+    import bench
+    a = bench.parse_args(["--gpus", "1", "--steps", "7", "--warmup", "2"])
+    assert a.full is False and a.dump_outputs == "" and a.detail is None and a.steps == 7 and a.warmup == 2
+    a = bench.parse_args(["--full", "--dump-outputs", "out"])
+    assert a.full is True and a.dump_outputs == "out"
+
+
+@pytest.mark.gpu
+@pytest.mark.timeout(600)
+def test_plain_run_times_the_steps_and_dumps_the_last_steps_pixels(tmp_path):
+    """`bench.py --gpus 1 --steps K --warmup W --dump-outputs DIR`: the contract line alone, with K timed steps, and image 0 of the
+    last step byte for byte what the oracle computes from the bench's synthetic coefficients."""
+    import numpy as np
+    sys.path.insert(0, ROOT)
+    sys.path.insert(0, os.path.join(ROOT, "oracle"))
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import jpeg_decoder_amd as J
+    import oracle as O
+    import synth
+    out = tmp_path / "dump"
+    r = _run(["--gpus", "1", "--steps", "3", "--warmup", "1", "--dump-outputs", str(out)], timeout=540)
+    assert r.returncode == 0, r.stderr[-2000:]
+    assert not [l for l in r.stdout.splitlines() if l.startswith("bench_detail:")]
+    line = json.loads(r.stdout.strip().splitlines()[-1])
+    assert line["steps"] == 3 and line["warmup"] == 1 and line["unit"] == "MP/s" and line["higher_is_better"] is True
+    assert line["dtype"] == "i32" and line["ms_per_step"] > 0 and line["value"] > 0
+    for k in ("k_4096", "scale_anchor", "e2e_summary", "cpu_baseline", "sustained_value"):
+        assert k not in line, k
+    files = sorted(os.listdir(out))
+    assert files == ["pixels_image0.npy", "pixels_sample.npy"]
+    assert sum(os.path.getsize(out / f) for f in files) <= 64 << 20
+    img0, sample = np.load(out / "pixels_image0.npy"), np.load(out / "pixels_sample.npy")
+    assert img0.dtype == sample.dtype == np.float32 and img0.shape == (1080, 1920, 3) and sample.size == 1 << 22
+    w, h, sampling = 1920, 1080, [(2, 2), (1, 1), (1, 1)]
+    ocomps, _ = O.make_components(w, h, sampling)
+    lum, chr_ = synth.quality_tables(85)
+    qts = [lum, chr_, chr_]
+    coefs = synth.coefficients_from_rgb(synth.synthetic_rgb(w, h), J.make_components(w, h, sampling)[0], "ycbcr", qts)
+    want = O.pixels_from_coefficients(ocomps, qts, coefs, w, h, "YCBCR").reshape(h, w, 3)
+    assert np.array_equal(img0, want.astype(np.float32))
+    # every image of the batch has these coefficients: each sampled byte is one of the picture's values
+    assert np.isin(sample, np.unique(want).astype(np.float32)).all()

@@ -8,7 +8,7 @@ cd $GRAFT_REPO_ROOT; O=gpurun_out/$N; mkdir -p $O
 export TRAFFIC_INSTALL=profiles/round6/pmc_traffic.json
 bash tools/gpu.sh $N tests
 bash tools/gpu.sh $N traffic:1080p-420:fused420:s420_kernel
-bash tools/gpu.sh $N "trace:bench_K:python+bench.py+--no-e2e+--no-k4096+--no-cpu-baseline+--no-scale-anchor+--min-seconds+0"
+bash tools/gpu.sh $N "trace:bench_K:python+bench.py+--full+--no-e2e+--no-k4096+--no-cpu-baseline+--no-scale-anchor+--min-seconds+0"
 bash tools/gpu.sh $N bench
 bash tools/gpu.sh $N forcedist
 bash tools/gpu.sh $N "pipe256:JPGPU_PIPE_ENTRY_PIXELS=1"
@@ -22,5 +22,5 @@ timeout 300 python tools/progw_asm_bench.py > $O/progw_asm_bench.txt 2>&1
   echo "== the dispatcher's own choice"; for n in 64 128 192 256 4096; do JPGPU_PIPE_TRACE=1 timeout 300 python tools/prog_calls.py --images $n --calls 2 --percent auto 2>&1 | grep "dispatcher:" | tail -1; done
   echo "== per scan (JPGPU_PROG_TIMES=1, 256 frames)"; JPGPU_PROG_TIMES=1 timeout 300 python tools/prog_calls.py --images 256 --calls 2 --percent 100 2>&1 | tail -15 ) > $O/progressive_calls.txt 2>&1
 bash tools/gpu.sh $N fuzz:300
-( for wl in 1080p-444 1080p-422 1080p-440 1080p-411 1080p-gray 1080p-cmyk 1080p-cmyk-2211 1080p-ycck-2212 1080p-420-scale4 1080p-420-scale2 1080p-420-scale1 1080p-444-scale4 1080p-444+gray 2160p-420; do timeout 300 python bench.py --workload $wl --steps 200 --warmup 30 --no-cpu-baseline --no-classes --min-seconds 0 2>/dev/null | tail -1; done ) > $O/other_workloads_bench.jsonl
+( for wl in 1080p-444 1080p-422 1080p-440 1080p-411 1080p-gray 1080p-cmyk 1080p-cmyk-2211 1080p-ycck-2212 1080p-420-scale4 1080p-420-scale2 1080p-420-scale1 1080p-444-scale4 1080p-444+gray 2160p-420; do timeout 300 python bench.py --full --workload $wl --steps 200 --warmup 30 --no-cpu-baseline --no-classes --min-seconds 0 2>/dev/null | tail -1; done ) > $O/other_workloads_bench.jsonl
 cp profiles/round6/pmc_traffic.json $O/pmc_traffic_installed.json
