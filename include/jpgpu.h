@@ -180,7 +180,8 @@ int jpgpu_batch_set_range_hint(jpgpu_batch *b, uint32_t image, int sane);
 int jpgpu_batch_set_range_class(jpgpu_batch *b, uint32_t image, uint32_t comp, int range_class);
 int jpgpu_range_class(const int16_t *coefficients, size_t len, const uint16_t quantization_table[64]);
 /* The same classification done ON THE DEVICE for every image of the batch, from the coefficients as they stand in the
- * arena (written there by the caller's own kernels or copies into a bound arena, or by the device entropy decoder):
+ * arena (written there by the caller's own kernels or copies into a bound arena, or by the device entropy decoder; compact
+ * uploads still waiting for a decode are expanded into it first, here and in jpgpu_batch_classify_on_device):
  * one pass over the arena at HBM speed on `hip_stream`, blocking; afterwards every component has the range class
  * jpgpu_batch_upload would have given it. If `classes` is not NULL it receives 4 entries per image. */
 int jpgpu_batch_scan_ranges(jpgpu_batch *b, void *hip_stream, uint8_t *classes);

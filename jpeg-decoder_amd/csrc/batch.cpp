@@ -115,6 +115,9 @@ struct jpgpu_batch {
     // Entry-list pixel path (fused_entries.hpp): images whose last device entropy launch kept their scan as entry lists.  entry_img[image]
     // = 1 until the host uploads coefficients for the image (a re-decode): the dense kernels skip it (CLS_SKIP), the decode that follows
     // the launch on its stream runs s420_entries_kernel over the plan(s) and copies the status words once more behind it.
+    // Every writer that makes the coefficient arena an image's source again drops the flag: per image, batch_drop_entry_image (host
+    // uploads dense or compact, classes set from the host); for the whole batch, batch_drop_entries (the device entropy and progressive
+    // launches, jpgpu_batch_classify_on_device).  A flag left behind has the next decode skip the image and return its old pixels.
     std::vector<uint8_t> entry_img;
     bool entries_pending = false;
     const EntrySrc *d_entry_srcs = nullptr;   // per batch image, inside d_entropy
@@ -150,11 +153,21 @@ static void batch_class_source(jpgpu_batch *b, size_t idx, bool from_device) {
     }
     if (from_device) b->dev_classes = true;
 }
-static void batch_set_host_class(jpgpu_batch *b, size_t idx, uint8_t cls) {
-    if (idx / 4 < b->entry_img.size() && b->entry_img[idx / 4]) {  // coefficients from the host: the image is a dense one again
-        b->entry_img[idx / 4] = 0;
+// the image's pixels come from the coefficient arena again (see entry_img)
+static void batch_drop_entry_image(jpgpu_batch *b, size_t image) {
+    if (image < b->entry_img.size() && b->entry_img[image]) {
+        b->entry_img[image] = 0;
         b->cls_dirty = true;
     }
+}
+// the same for every image, and no entry-list walk owed to an earlier launch
+static void batch_drop_entries(jpgpu_batch *b) {
+    if (b->entry_img.size() != b->descs.size()) b->entry_img.assign(b->descs.size(), 0);
+    for (size_t i = 0; i < b->entry_img.size(); i++) batch_drop_entry_image(b, i);
+    b->entries_pending = false;
+}
+static void batch_set_host_class(jpgpu_batch *b, size_t idx, uint8_t cls) {
+    batch_drop_entry_image(b, idx / 4);  // coefficients from the host: the image is a dense one again
     if (b->sane[idx] != cls) {
         b->sane[idx] = cls;
         b->cls_dirty = true;
@@ -537,12 +550,24 @@ static int batch_scan_jobs(jpgpu_batch *b, uint32_t &n_jobs, uint32_t &max_block
     return JPGPU_OK;
 }
 
+static int batch_expand_pending(jpgpu_batch *b, hipStream_t s);
+
+// Compact uploads reach the arena at the next decode; a pass that classifies "the coefficients as they stand in the arena" expands
+// them first, or it would classify what the images held before (tables first: the expansion ranges unclassified uploads with them)
+static int batch_settle_arena(jpgpu_batch *b, hipStream_t s) {
+    int rc = batch_refresh_jobs(b, s);
+    if (rc) return rc;
+    return batch_expand_pending(b, s);
+}
+
 int jpgpu_batch_scan_ranges(jpgpu_batch *b, void *hip_stream, uint8_t *classes) {
     if (!b) return JPGPU_ERR_FORMAT;
     int rc = use_device(b->device, b->err);
     if (rc) return rc;
     if (!b->d_coef) return set_err(b->err, JPGPU_ERR_FORMAT, "batch has no device buffers bound");
     hipStream_t s = (hipStream_t)hip_stream;
+    rc = batch_settle_arena(b, s);
+    if (rc) return rc;
     // stats and job table live on the device between calls (a call per decode must not allocate: bench.py times it)
     uint32_t max_blocks = 0, n_jobs = 0;
     size_t jobs_off = 0;
@@ -577,6 +602,9 @@ int jpgpu_batch_classify_on_device(jpgpu_batch *b, void *hip_stream) {
     hipStream_t s = (hipStream_t)hip_stream;
     rc = batch_enable_dev_classes(b);
     if (rc) return rc;
+    rc = batch_settle_arena(b, s);
+    if (rc) return rc;
+    batch_drop_entries(b);  // (the caller declares the arena the images' source)
     uint32_t max_blocks = 0, n_jobs = 0;
     size_t jobs_off = 0;
     rc = batch_scan_jobs(b, n_jobs, max_blocks, jobs_off);
@@ -621,6 +649,11 @@ int jpgpu_batch_upload(jpgpu_batch *b, uint32_t image, uint32_t comp, const int1
     if (!(b->flags & JPGPU_BATCH_ASSUME_HOSTILE))
         sane = (uint8_t)jpgpu_range_class(coefficients, len, b->descs[image].quantization_tables[comp]);
     batch_set_host_class(b, (size_t)image * 4 + comp, sane);
+    {
+        // a compact upload of this component still waiting for its expansion is superseded: the last upload before a decode wins
+        std::lock_guard<std::mutex> g(b->compact_mutex);
+        if (!b->compact_pending.empty()) b->compact_pending[(size_t)image * 4 + comp] = 0;
+    }
     B_HIP(hipMemcpy(b->d_coef + b->coef_off[image * 4 + comp], coefficients, len * sizeof(int16_t), hipMemcpyHostToDevice));
     return JPGPU_OK;
 }
@@ -673,6 +706,7 @@ int jpgpu::batch_upload_compact(jpgpu_batch *b, uint32_t image, uint32_t comp, c
         } else {
             rc = batch_enable_dev_classes(b);
             if (rc) return rc;
+            batch_drop_entry_image(b, image);  // (what batch_set_host_class does in the other branch)
             b->sane[idx] = 0;
             // (the whole plane is replaced and ranged, at expansion time, with the table the device then holds — batch_refresh_jobs
             // runs first; older maxima only over-estimate)
@@ -873,10 +907,7 @@ int jpgpu::batch_device_entropy_launch(jpgpu_batch *b, const DeviceEntropyImage 
         for (const FusedPlan &fp : b->fused)
             if (fp.kind == FUSED_420 && fp.strip)
                 for (uint32_t i = 0; i < fp.n_images; i++) walk_geom[fp.ids[i]] = &fp.geoms[i];
-    if (b->entry_img.size() != b->descs.size()) b->entry_img.assign(b->descs.size(), 0);
-    for (uint8_t &e : b->entry_img)
-        if (e) e = 0, b->cls_dirty = true;
-    b->entries_pending = false;
+    batch_drop_entries(b);
     size_t n_raw_jobs = 0;
     uint32_t max_pieces = 0, light_images = 0;
     constexpr size_t PINNED_SPAN_GAP_MAX = 4096u;  // (bytes; below one page: see where the spans are built)
@@ -1361,6 +1392,7 @@ int jpgpu::batch_device_progressive_launch(jpgpu_batch *b, const DeviceProgressi
     hipStream_t s = (hipStream_t)hip_stream;
     rc = batch_enable_dev_classes(b);
     if (rc) return rc;
+    batch_drop_entries(b);  // (the frames' coefficients go to the arena: a sub-batch reused after an entry-list call must not skip them)
     size_t n_scans = 0, n_tracks = 0, n_tables = 0, data_bytes = 0, mask_bytes = 0;
     for (uint32_t k = 0; k < n; k++) {
         if (images[k].image >= b->descs.size() || !images[k].plan || !images[k].file) return set_err(b->err, JPGPU_ERR_FORMAT, "device progressive: bad image");
