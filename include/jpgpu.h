@@ -145,6 +145,22 @@ enum {
 
 int jpgpu_batch_create(int device, const jpgpu_image_desc *descs, uint32_t n_images,
                        uint32_t flags, jpgpu_batch **out);
+/* A window of each image's output: (x, y, w, h) in the pixel grid of the image's output (out_w x out_h, after Decoder::scale;
+ * for one component the component's size, as compute_image has it).  w == 0 or h == 0: the whole image. */
+typedef struct jpgpu_window {
+    uint16_t x, y, w, h;
+} jpgpu_window;
+/* jpgpu_batch_create with a window per image (`windows` NULL: exactly jpgpu_batch_create).  The pixels of image i are then the
+ * window's rows and columns of the whole decode, in the same pixel format, packed (row pitch w * ncomp bytes):
+ *   interleaving colour functions        full.reshape(H, W, nc)[y:y+h, x:x+w]
+ *   ColorTransform None, > 1 component   full.reshape(H, nc, W)[y:y+h, :, x:x+w]   (color_no_convert: planar within a row)
+ * jpgpu_batch_out_bytes / out_offset, the output arena and jpgpu_batch_download hold the window's bytes; the coefficient arena
+ * stays whole-image.  A window that covers the whole image is no window (same route, same kernels, same bytes).  Windowed images
+ * run a kernel of their own (jpgpu_batch_path: "window", or "mixed" with other images) with exact arithmetic at every scale.
+ * A window that does not lie inside its image fails creation with JPGPU_ERR_FORMAT; a hand-made descriptor the window planner
+ * refuses (components at different dct_scales) with JPGPU_ERR_UNSUPPORTED and the reason in jpgpu_batch_last_error. */
+int jpgpu_batch_create_windowed(int device, const jpgpu_image_desc *descs, const jpgpu_window *windows, uint32_t n_images,
+                                uint32_t flags, jpgpu_batch **out);
 void jpgpu_batch_destroy(jpgpu_batch *b);
 const char *jpgpu_batch_last_error(const jpgpu_batch *b);
 

@@ -65,6 +65,11 @@ class ImageDesc(C.Structure):
     ]
 
 
+class Window(C.Structure):
+    """jpgpu_window: (x, y, w, h) in the image's output grid; w == 0 or h == 0 = the whole image."""
+    _fields_ = [("x", C.c_uint16), ("y", C.c_uint16), ("w", C.c_uint16), ("h", C.c_uint16)]
+
+
 class PipelineTimings(C.Structure):
     _fields_ = [(n, C.c_double) for n in ("headers_ms", "setup_ms", "entropy_and_upload_ms", "kernels_ms", "download_ms", "total_ms")] + \
                [("threads", C.c_uint32), ("images_ok", C.c_uint32), ("jpeg_bytes", C.c_uint64), ("coefficient_bytes", C.c_uint64),
@@ -117,6 +122,7 @@ _PROTOS = {
     "jpgpu_compute_image": (C.c_int, [C.c_void_p, C.POINTER(Component), C.c_uint32, C.POINTER(C.c_void_p), C.c_uint16,
                                       C.c_uint16, C.c_int, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]),
     "jpgpu_batch_create": (C.c_int, [C.c_int, C.POINTER(ImageDesc), C.c_uint32, C.c_uint32, C.POINTER(C.c_void_p)]),
+    "jpgpu_batch_create_windowed": (C.c_int, [C.c_int, C.POINTER(ImageDesc), C.POINTER(Window), C.c_uint32, C.c_uint32, C.POINTER(C.c_void_p)]),
     "jpgpu_batch_destroy": (None, [C.c_void_p]),
     "jpgpu_batch_last_error": (C.c_char_p, [C.c_void_p]),
     "jpgpu_batch_coef_arena_bytes": (C.c_size_t, [C.c_void_p]),

@@ -21,11 +21,43 @@ def image_desc(components, quantization_tables, out_w, out_h, color_transform):
     return d
 
 
+def window_structs(windows, n):
+    """`windows`: None, one (x, y, w, h) for every image, or a list with a tuple or None per image -> jpgpu_window[n] (or None)."""
+    if windows is None:
+        return None
+    if len(windows) == 4 and all(isinstance(v, (int, np.integer)) for v in windows):
+        windows = [tuple(windows)] * n
+    if len(windows) != n:
+        raise ValueError(f"{len(windows)} windows for {n} images")
+    arr = (N.Window * n)()
+    for i, w in enumerate(windows):
+        if w is not None:
+            x, y, ww, hh = (int(v) for v in w)
+            if min(x, y, ww, hh) < 0 or max(x, y, ww, hh) > 65535:
+                raise ValueError(f"window {w!r} of image {i}")
+            arr[i].x, arr[i].y, arr[i].w, arr[i].h = x, y, ww, hh
+    return arr
+
+
 class Batch:
-    def __init__(self, descs, device=0, flags=N.BATCH_DEFAULT):
+    """N independent images decoded per launch (jpgpu_batch_*).
+
+    windows: None, one (x, y, w, h) for every image, or a list with a tuple or None per image.  A window lies in the pixel grid
+    of the image's output (out_w x out_h after a scale; for one component the component's size); the image's pixels are then
+    the window's rows and columns of the whole decode, packed (row pitch w * ncomp bytes):
+    ``full.reshape(H, W, nc)[y:y+h, x:x+w]`` for interleaving colour functions, ``full.reshape(H, nc, W)[y:y+h, :, x:x+w]`` for
+    ColorTransform None with more than one component.  out_bytes / download / the output arena hold the window's bytes.  A
+    window that covers the whole image (or None, or w == 0 or h == 0) is no window; one outside its image fails creation
+    (FormatError)."""
+
+    def __init__(self, descs, device=0, flags=N.BATCH_DEFAULT, windows=None):
         self._h = C.c_void_p()
         arr = (N.ImageDesc * len(descs))(*descs)
-        st = N.lib().jpgpu_batch_create(device, arr, len(descs), flags, C.byref(self._h))
+        wins = window_structs(windows, len(descs))
+        if wins is None:
+            st = N.lib().jpgpu_batch_create(device, arr, len(descs), flags, C.byref(self._h))
+        else:
+            st = N.lib().jpgpu_batch_create_windowed(device, arr, wins, len(descs), flags, C.byref(self._h))
         if st:
             msg = N.lib().jpgpu_batch_last_error(self._h) if self._h else b"jpgpu_batch_create"
             msg = bytes(msg)
@@ -33,6 +65,7 @@ class Batch:
             check(st, msg)
         self.n_images = len(descs)
         self.descs = descs
+        self.windows = None if wins is None else [None if (w.w == 0 or w.h == 0) else (w.x, w.y, w.w, w.h) for w in wins]
 
     def close(self):
         if getattr(self, "_h", None):

@@ -30,6 +30,7 @@
 #include "host_common.hpp"
 #include "kernels.hpp"
 #include "range_stats.hpp"
+#include "window_band.hpp"
 
 using namespace jpgpu;
 
@@ -72,6 +73,18 @@ struct jpgpu_batch {
     uint32_t s_max_tiles_x = 0, s_max_bands = 0, s_lds_bytes = 0;
     bool s_scales[9] = {false, false, false, false, false, false, false, false, false};
     std::string scaled_name;            // path name of the scaled launch group ("fused420-s4", ...; "fusedscaled-mixed")
+    // Windows (jpgpu_batch_create_windowed, window_band.hpp): images with a window smaller than the image form a group of their own —
+    // never in a fused plan, the scaled or the generic group.  Their coefficients are whole-image arena entries as ever, their output
+    // is the window's bytes; the kernel works with exact arithmetic at every scale, so their range classes play no part.
+    std::vector<uint32_t> win_ids;
+    std::vector<WindowGeom> win_geoms;
+    std::vector<PlaneJob> w_plane_jobs;
+    std::vector<ImageJob> w_image_jobs;
+    WindowGeom *d_win_geoms = nullptr;
+    PlaneJob *d_w_plane_jobs = nullptr;
+    ImageJob *d_w_image_jobs = nullptr;
+    uint32_t w_max_tiles_x = 0, w_max_bands = 0, w_lds_bytes = 0;
+    bool w_scales[9] = {false, false, false, false, false, false, false, false, false};
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
     // compact transport (compact.hpp): staging area in HBM, allocated at the first jpgpu_batch_upload_compact
     std::mutex compact_mutex;
@@ -252,6 +265,30 @@ static int batch_refresh_jobs(jpgpu_batch *b, hipStream_t stream = nullptr) {
         B_HIP(hipMemcpy(b->d_s_plane_jobs, b->s_plane_jobs.data(), b->s_plane_jobs.size() * sizeof(PlaneJob), hipMemcpyHostToDevice));
         B_HIP(hipMemcpy(b->d_s_image_jobs, b->s_image_jobs.data(), b->s_image_jobs.size() * sizeof(ImageJob), hipMemcpyHostToDevice));
     }
+    b->w_plane_jobs.clear();
+    b->w_image_jobs.clear();
+    for (uint32_t i : b->win_ids) {  // (as the scaled group: planes in LDS; job.out = the window's bytes)
+        const jpgpu_image_desc &d = b->descs[i];
+        uint8_t *no_planes[4] = {nullptr, nullptr, nullptr, nullptr};
+        for (uint32_t c = 0; c < d.ncomp; c++) {
+            PlaneJob j{};
+            j.coefs = reinterpret_cast<const int16_t *>(b->d_coef + b->coef_off[i * 4 + c]);
+            j.qt = b->d_qt + ((size_t)i * 4 + c) * 64;
+            j.block_w = d.components[c].block_width;
+            j.n_blocks = (uint32_t)d.components[c].block_width * d.components[c].block_height;
+            j.scale = d.components[c].dct_scale;
+            b->w_plane_jobs.push_back(j);
+        }
+        ImageJob ij;
+        size_t out_len = 0;
+        int rc = build_image_job(d.components, d.ncomp, no_planes, d.out_w, d.out_h, d.color_transform, b->d_out + b->out_off[i], ij, out_len, b->err);
+        if (rc) return rc;
+        b->w_image_jobs.push_back(ij);
+    }
+    if (!b->w_plane_jobs.empty()) {
+        B_HIP(hipMemcpy(b->d_w_plane_jobs, b->w_plane_jobs.data(), b->w_plane_jobs.size() * sizeof(PlaneJob), hipMemcpyHostToDevice));
+        B_HIP(hipMemcpy(b->d_w_image_jobs, b->w_image_jobs.data(), b->w_image_jobs.size() * sizeof(ImageJob), hipMemcpyHostToDevice));
+    }
     for (FusedPlan &fp : b->fused) {
         int rc = fused_bind(fp, b->d_coef, b->d_out, b->d_qt, b->coef_off, b->out_off, b->sane, b->err);
         if (rc) return rc;
@@ -270,8 +307,8 @@ static int batch_refresh_jobs(jpgpu_batch *b, hipStream_t stream = nullptr) {
 
 extern "C" {
 
-int jpgpu_batch_create(int device, const jpgpu_image_desc *descs, uint32_t n_images, uint32_t flags,
-                       jpgpu_batch **out) {
+static int batch_create(int device, const jpgpu_image_desc *descs, const jpgpu_window *windows, uint32_t n_images, uint32_t flags,
+                        jpgpu_batch **out) {
     if (!out) return JPGPU_ERR_FORMAT;
     *out = nullptr;
     if (!descs || n_images == 0 || n_images > 65535) return JPGPU_ERR_FORMAT;
@@ -304,11 +341,35 @@ int jpgpu_batch_create(int device, const jpgpu_image_desc *descs, uint32_t n_ima
         size_t out_len = 0;
         rc = build_image_job(d.components, d.ncomp, dummy, d.out_w, d.out_h, d.color_transform, nullptr, ij, out_len, b->err);
         if (rc) return rc;
+        // a window smaller than the image: the window group (an empty window or one that covers the image is no window)
+        bool windowed = false;
+        if (windows && windows[i].w != 0 && windows[i].h != 0) {
+            const jpgpu_window &wn = windows[i];
+            uint32_t gw = 0, gh = 0;
+            window_grid(d.components, d.ncomp, d.out_w, d.out_h, gw, gh);
+            if ((uint32_t)wn.x + wn.w > gw || (uint32_t)wn.y + wn.h > gh)
+                return set_err(b->err, JPGPU_ERR_FORMAT, "image %u: window (%u, %u) %ux%u outside the %ux%u image", i, wn.x, wn.y, wn.w, wn.h, gw, gh);
+            if (wn.x != 0 || wn.y != 0 || wn.w != gw || wn.h != gh) {
+                WindowGeom wg;
+                const char *why = "";
+                if (!window_geom_from_job(d.components, d.ncomp, ij, wn.x, wn.y, wn.w, wn.h, wg, why))
+                    return set_err(b->err, JPGPU_ERR_UNSUPPORTED, "image %u: no window kernel for this descriptor: %s", i, why);
+                windowed = true;
+                kind_key[i] = 0;
+                b->win_ids.push_back(i);
+                b->win_geoms.push_back(wg);
+                b->w_max_tiles_x = std::max(b->w_max_tiles_x, wg.tiles_x);
+                b->w_max_bands = std::max(b->w_max_bands, wg.bands);
+                b->w_lds_bytes = std::max(b->w_lds_bytes, wg.lds_bytes);
+                b->w_scales[wg.scale] = true;
+                out_len = (size_t)wn.w * wn.h * d.ncomp;
+            }
+        }
         // reduced-size decodes (every component at one dct_scale < 8): one launch, planes in LDS (fused_scaled.hpp)
         ScaledGeom sg;
         static const uint32_t scaled_tx = getenv("JPGPU_SCALED_TX") ? (uint32_t)std::max(8, atoi(getenv("JPGPU_SCALED_TX"))) : 64u;  // (tuning / test knob)
         static const uint32_t scaled_ry = getenv("JPGPU_SCALED_RY") ? (uint32_t)std::max(1, atoi(getenv("JPGPU_SCALED_RY"))) : 8u;
-        const bool scaled = kind_key[i] == 0 && !(flags & JPGPU_BATCH_FORCE_GENERIC) && scaled_geom_from_job(d.components, d.ncomp, ij, sg, scaled_tx, scaled_ry);
+        const bool scaled = !windowed && kind_key[i] == 0 && !(flags & JPGPU_BATCH_FORCE_GENERIC) && scaled_geom_from_job(d.components, d.ncomp, ij, sg, scaled_tx, scaled_ry);
         if (scaled) {
             b->scaled_ids.push_back(i);
             b->scaled_geoms.push_back(sg);
@@ -326,7 +387,7 @@ int jpgpu_batch_create(int device, const jpgpu_image_desc *descs, uint32_t n_ima
             b->coef_off[i * 4 + c] = co;
             b->coef_len[i * 4 + c] = cb;
             co += align_up(cb, 256);
-            if (kind_key[i] == 0 && !scaled) {  // generic path: intermediate u8 plane, launch extents
+            if (kind_key[i] == 0 && !scaled && !windowed) {  // generic path: intermediate u8 plane, launch extents
                 b->plane_off[i * 4 + c] = po;
                 po += align_up(plane_bytes(cc), 256);
                 b->max_blocks = std::max<uint32_t>(b->max_blocks, (uint32_t)cc.block_width * cc.block_height);
@@ -336,7 +397,7 @@ int jpgpu_batch_create(int device, const jpgpu_image_desc *descs, uint32_t n_ima
         b->out_off[i] = oo;
         b->out_len[i] = out_len;
         oo += align_up(out_len, 256);
-        if (kind_key[i] == 0 && !scaled) {
+        if (kind_key[i] == 0 && !scaled && !windowed) {
             b->generic_ids.push_back(i);
             b->max_w = std::max<uint32_t>(b->max_w, d.ncomp == 1 ? d.components[0].size_width : d.out_w);
             b->max_h = std::max<uint32_t>(b->max_h, d.ncomp == 1 ? d.components[0].size_height : d.out_h);
@@ -363,11 +424,13 @@ int jpgpu_batch_create(int device, const jpgpu_image_desc *descs, uint32_t n_ima
             if (!fused_plan(sub, ids, fp, why)) return set_err(b->err, JPGPU_ERR_INTERNAL, "fused plan: %s", why.c_str());
             b->fused.push_back(std::move(fp));
         }
-        if (b->fused.empty()) b->path = "generic";
+        if (b->fused.empty()) b->path = b->generic_ids.empty() ? "" : "generic";
         else if (b->fused.size() == 1 && b->generic_ids.empty()) b->path = b->fused[0].name;
         else b->path = "mixed";
     }
     if (!b->scaled_ids.empty()) b->path = (b->fused.empty() && b->generic_ids.empty()) ? b->scaled_name : "mixed";
+    if (!b->win_ids.empty()) b->path = b->path.empty() ? "window" : "mixed";
+    if (b->path.empty()) b->path = "generic";
     hipError_t e;
 #define C_HIP(call)                                                                        \
     if ((e = (call)) != hipSuccess) return set_err(b->err, JPGPU_ERR_IO, "%s: %s", #call, hipGetErrorString(e))
@@ -404,10 +467,30 @@ int jpgpu_batch_create(int device, const jpgpu_image_desc *descs, uint32_t n_ima
         C_HIP(hipMalloc((void **)&b->d_s_plane_jobs, ns * 4 * sizeof(PlaneJob)));
         C_HIP(hipMalloc((void **)&b->d_s_image_jobs, ns * sizeof(ImageJob)));
     }
+    if (!b->win_ids.empty()) {
+        const size_t nw = b->win_ids.size();
+        uint32_t pj = 0;
+        for (size_t k = 0; k < nw; k++) {
+            b->win_geoms[k].first_plane_job = pj;
+            pj += b->descs[b->win_ids[k]].ncomp;
+        }
+        C_HIP(hipMalloc((void **)&b->d_win_geoms, nw * sizeof(WindowGeom)));
+        C_HIP(hipMemcpy(b->d_win_geoms, b->win_geoms.data(), nw * sizeof(WindowGeom), hipMemcpyHostToDevice));
+        C_HIP(hipMalloc((void **)&b->d_w_plane_jobs, nw * 4 * sizeof(PlaneJob)));
+        C_HIP(hipMalloc((void **)&b->d_w_image_jobs, nw * sizeof(ImageJob)));
+    }
     C_HIP(hipEventCreate(&b->ev0));
     C_HIP(hipEventCreate(&b->ev1));
 #undef C_HIP
     return JPGPU_OK;
+}
+
+int jpgpu_batch_create(int device, const jpgpu_image_desc *descs, uint32_t n_images, uint32_t flags, jpgpu_batch **out) {
+    return batch_create(device, descs, nullptr, n_images, flags, out);
+}
+int jpgpu_batch_create_windowed(int device, const jpgpu_image_desc *descs, const jpgpu_window *windows, uint32_t n_images, uint32_t flags,
+                                jpgpu_batch **out) {
+    return batch_create(device, descs, windows, n_images, flags, out);
 }
 
 void jpgpu_batch_destroy(jpgpu_batch *b) {
@@ -442,6 +525,9 @@ void jpgpu_batch_destroy(jpgpu_batch *b) {
         if (b->d_scaled_geoms) hipFree(b->d_scaled_geoms);
         if (b->d_s_plane_jobs) hipFree(b->d_s_plane_jobs);
         if (b->d_s_image_jobs) hipFree(b->d_s_image_jobs);
+        if (b->d_win_geoms) hipFree(b->d_win_geoms);
+        if (b->d_w_plane_jobs) hipFree(b->d_w_plane_jobs);
+        if (b->d_w_image_jobs) hipFree(b->d_w_image_jobs);
         for (FusedPlan &fp : b->fused) fused_free(fp);
         if (b->ev0) hipEventDestroy(b->ev0);
         if (b->ev1) hipEventDestroy(b->ev1);
@@ -1801,6 +1887,9 @@ int jpgpu_batch_decode(jpgpu_batch *b, void *hip_stream) {
             if (b->scales[sc]) B_HIP(launch_idct_planes(b->d_plane_jobs, (uint32_t)b->plane_jobs.size(), b->max_blocks, sc, s));
         B_HIP(launch_upsample_color(b->d_image_jobs, n, b->max_w, b->max_h, s));
     }
+    if (!b->win_ids.empty())  // (windows: after the others)
+        B_HIP(launch_window_band(b->d_win_geoms, b->d_w_image_jobs, b->d_w_plane_jobs, (uint32_t)b->win_ids.size(), b->w_max_tiles_x, b->w_max_bands,
+                                 b->w_lds_bytes, b->w_scales, s));
     if (b->phase_events_valid) B_HIP(hipEventRecord(b->ev_phase[5], s));
     return JPGPU_OK;
 }
