@@ -57,6 +57,14 @@ int jpgpu_decoder_decode(jpgpu_decoder *d, uint8_t *dst, size_t cap, size_t *len
 /* Size decode() will produce, valid after read_info: width*height*bytes_per_pixel. */
 size_t jpgpu_decoder_output_bytes(const jpgpu_decoder *d);
 
+/* A window of the output instead of the whole image: decode() returns the rows and columns (x, y, w, h) of the whole decode, packed,
+ * as jpgpu_batch_create_windowed (jpgpu.h) defines them; w or h 0: the whole image again.  Only stored here; decode() checks it
+ * against the output size in force then (after scale): a window that does not lie inside fails with JPGPU_ERR_FORMAT and nothing
+ * is decoded.  jpgpu_decoder_output_bytes is the window's byte count once the info is known.  Both routes honour it: retained
+ * coefficients through a one-image windowed batch for small images, the one-image device-entropy pipeline for sequential images of
+ * 0.9 MP and more (a window alone does not take an image off that route).  info() and the metadata accessors are untouched. */
+int jpgpu_decoder_set_window(jpgpu_decoder *d, uint16_t x, uint16_t y, uint16_t w, uint16_t h);
+
 /* Metadata — src/decoder.rs:200-243. Pointers stay valid until the decoder is destroyed;
  * NULL/0 when absent.  icc_profile assembles the APP2 chunks (validity rules of :213-243). */
 const uint8_t *jpgpu_decoder_exif_data(const jpgpu_decoder *d, size_t *len);
@@ -125,6 +133,8 @@ typedef struct jpgpu_pipeline_timings {
     uint32_t images_device_progressive; /* of images_device_entropy: progressive frames whose scans were decoded and accumulated on the device */
     uint32_t images_entry_pixels; /* (round 6, in what was padding) of images_device_entropy: 4:2:0 images whose pixel walk read the chunk
                                    * decoder's entry lists itself — nothing of their scan went through the coefficient arena */
+    /* ---- appended with jpgpu_pipeline_decode_windowed ---- */
+    uint32_t images_windowed;     /* decoded images that ran the window kernel (a window smaller than their output) */
 } jpgpu_pipeline_timings;
 
 enum {
@@ -216,6 +226,24 @@ int jpgpu_pipeline_set_max_decoding_buffer_size(jpgpu_pipeline *p, size_t max_by
  * when individual images failed. */
 int jpgpu_pipeline_decode(jpgpu_pipeline *p, const uint8_t *const *data, const size_t *len, uint32_t n_images,
                           uint32_t flags);
+/* jpgpu_pipeline_decode with a window per image.  `windows` NULL: exactly jpgpu_pipeline_decode.  windows[i] is a jpgpu_window
+ * (jpgpu.h) in the pixel grid of image i's OUTPUT — after jpgpu_pipeline_set_scale chose the image's DCT scale; for a one-component
+ * image the component's size; w == 0 or h == 0: the whole image; a window that covers the whole image is no window (same route,
+ * same kernels, same bytes).  The pixels of image i are that slice of its whole decode, packed, as jpgpu_batch_create_windowed
+ * defines it; jpgpu_pipeline_pixel_bytes / _pixels_device / _pixels_host / _download, the JPGPU_PIPELINE_DOWNLOAD and
+ * JPGPU_PIPELINE_GATHER copies and timings.pixel_bytes hold / count the WINDOW's bytes, jpgpu_pipeline_image_info keeps reporting
+ * the image's (scaled) size.  No clipping: a window that does not lie inside its image's output gives THAT image JPGPU_ERR_FORMAT
+ * (a descriptor the window planner refuses: JPGPU_ERR_UNSUPPORTED); every other image of the call is decoded.  The stream is still
+ * entropy-decoded whole on every route (host, device, progressive, multi-device): an image's status with a window is its status
+ * without one.  A windowed 4:2:0 image never takes the entry-list pixel walk (timings.images_entry_pixels counts the unwindowed
+ * ones only).  Kept sub-batches are reused as they are only while their windows repeat as well; other windows for the same set of
+ * windowed images (fresh random crops) are set in place, any other change creates the sub-batch anew.  (In a sub-batch re-windowed in
+ * place an image whose new window covers its whole output stays with the window kernel: same bytes; timings.images_windowed counts it.) */
+int jpgpu_pipeline_decode_windowed(jpgpu_pipeline *p, const uint8_t *const *data, const size_t *len, const jpgpu_window *windows,
+                                   uint32_t n_images, uint32_t flags);
+/* The window image i of the last call was decoded with: what the caller passed, or 0, 0, W, H of the output grid when it had none
+ * (JPGPU_ERR_FORMAT for an image without a frame or whose window was refused). */
+int jpgpu_pipeline_image_window(const jpgpu_pipeline *p, uint32_t image, jpgpu_window *out);
 /* Results of the last decode call, valid until the next one / destroy. */
 int jpgpu_pipeline_image_status(const jpgpu_pipeline *p, uint32_t image);        /* JPGPU_OK or the image's error */
 const char *jpgpu_pipeline_image_error(const jpgpu_pipeline *p, uint32_t image); /* its message */

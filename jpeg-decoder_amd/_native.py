@@ -77,7 +77,7 @@ class PipelineTimings(C.Structure):
                 ("dev_times_valid", C.c_uint32), ("_pad", C.c_uint32)] + \
                [(n, C.c_double) for n in ("dev_fill_ms", "dev_sync_ms", "dev_write_ms", "dev_pixel_ms", "decode_ms", "gather_ms")] + \
                [("gather_bytes", C.c_uint64), ("gather_copy_ms", C.c_double), ("cpu_ms", C.c_double), ("images_host_light", C.c_uint32),
-                ("input_pinned", C.c_uint32), ("images_device_progressive", C.c_uint32), ("images_entry_pixels", C.c_uint32)]
+                ("input_pinned", C.c_uint32), ("images_device_progressive", C.c_uint32), ("images_entry_pixels", C.c_uint32), ("images_windowed", C.c_uint32)]
 
 
 PIPELINE_DOWNLOAD, PIPELINE_DENSE, PIPELINE_DEVICE_ENTROPY, PIPELINE_GATHER = 1, 2, 4, 16
@@ -161,6 +161,7 @@ _PROTOS = {
     "jpgpu_decoder_scale": (C.c_int, [C.c_void_p, C.c_uint16, C.c_uint16, C.POINTER(C.c_uint16), C.POINTER(C.c_uint16)]),
     "jpgpu_decoder_decode": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]),
     "jpgpu_decoder_output_bytes": (C.c_size_t, [C.c_void_p]),
+    "jpgpu_decoder_set_window": (C.c_int, [C.c_void_p, C.c_uint16, C.c_uint16, C.c_uint16, C.c_uint16]),
     "jpgpu_decoder_exif_data": (C.c_void_p, [C.c_void_p, C.POINTER(C.c_size_t)]),
     "jpgpu_decoder_xmp_data": (C.c_void_p, [C.c_void_p, C.POINTER(C.c_size_t)]),
     "jpgpu_decoder_icc_profile": (C.c_void_p, [C.c_void_p, C.POINTER(C.c_size_t)]),
@@ -178,6 +179,8 @@ _PROTOS = {
     "jpgpu_pipeline_last_error": (C.c_char_p, [C.c_void_p]),
     "jpgpu_trim_caches": (None, []),
     "jpgpu_pipeline_decode": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), C.c_uint32, C.c_uint32]),
+    "jpgpu_pipeline_decode_windowed": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), C.POINTER(Window), C.c_uint32, C.c_uint32]),
+    "jpgpu_pipeline_image_window": (C.c_int, [C.c_void_p, C.c_uint32, C.POINTER(Window)]),
     "jpgpu_pipeline_image_status": (C.c_int, [C.c_void_p, C.c_uint32]),
     "jpgpu_pipeline_image_error": (C.c_char_p, [C.c_void_p, C.c_uint32]),
     "jpgpu_pipeline_image_info": (C.c_int, [C.c_void_p, C.c_uint32, C.POINTER(ImageInfoStruct)]),

@@ -45,6 +45,8 @@ struct jpgpu_batch {
     std::vector<size_t> coef_len;   // bytes
     std::vector<size_t> plane_off;  // [image*4 + comp] (generic path scratch)
     std::vector<size_t> out_off, out_len;
+    std::vector<size_t> out_full_len;  // per image: bytes of its whole output (out_len of an image without a window)
+    size_t out_cap = 0;                // bytes allocated behind d_out (own_out; >= out_bytes: batch_rewindow)
     size_t coef_bytes = 0, out_bytes = 0, plane_bytes_total = 0;
     uint8_t *d_coef = nullptr, *d_out = nullptr;
     bool own_coef = false, own_out = false;
@@ -324,6 +326,7 @@ static int batch_create(int device, const jpgpu_image_desc *descs, const jpgpu_w
     b->plane_off.assign((size_t)n_images * 4, 0);
     b->out_off.assign(n_images, 0);
     b->out_len.assign(n_images, 0);
+    b->out_full_len.assign(n_images, 0);
     b->sane.assign((size_t)n_images * 4, 0);
     b->cls_src.assign((size_t)n_images * 4, 0);
     // path resolution: group the images that can share a fused launch, the rest is generic
@@ -341,6 +344,7 @@ static int batch_create(int device, const jpgpu_image_desc *descs, const jpgpu_w
         size_t out_len = 0;
         rc = build_image_job(d.components, d.ncomp, dummy, d.out_w, d.out_h, d.color_transform, nullptr, ij, out_len, b->err);
         if (rc) return rc;
+        b->out_full_len[i] = out_len;
         // a window smaller than the image: the window group (an empty window or one that covers the image is no window)
         bool windowed = false;
         if (windows && windows[i].w != 0 && windows[i].h != 0) {
@@ -437,7 +441,11 @@ static int batch_create(int device, const jpgpu_image_desc *descs, const jpgpu_w
     if (!(flags & JPGPU_BATCH_EXTERNAL_BUFFERS)) {
         C_HIP(hipMalloc((void **)&b->d_coef, b->coef_bytes));
         b->own_coef = true;
-        C_HIP(hipMalloc((void **)&b->d_out, b->out_bytes));
+        // (with windows: a quarter more than these need, at most what the whole images take — batch_rewindow sets other windows in place)
+        size_t full = 0;
+        for (size_t v : b->out_full_len) full += align_up(v, 256);
+        b->out_cap = b->win_ids.empty() ? b->out_bytes : std::max(b->out_bytes, std::min(std::max<size_t>(full, 256), b->out_bytes + b->out_bytes / 4));
+        C_HIP(hipMalloc((void **)&b->d_out, b->out_cap));
         b->own_out = true;
     }
     if (!b->generic_ids.empty()) C_HIP(hipMalloc((void **)&b->d_planes, b->plane_bytes_total));
@@ -994,6 +1002,9 @@ int jpgpu::batch_device_entropy_launch(jpgpu_batch *b, const DeviceEntropyImage 
             if (fp.kind == FUSED_420 && fp.strip)
                 for (uint32_t i = 0; i < fp.n_images; i++) walk_geom[fp.ids[i]] = &fp.geoms[i];
     batch_drop_entries(b);
+    // Windowed images: which rows of their scan the window kernel reads (the others need not reach the arena)
+    std::vector<const WindowGeom *> win_geom((mode & DEVICE_ENTROPY_WINDOW_ROWS) && !b->win_ids.empty() ? b->descs.size() : 0, nullptr);
+    for (size_t k = 0; k < b->win_ids.size() && !win_geom.empty(); k++) win_geom[b->win_ids[k]] = &b->win_geoms[k];
     size_t n_raw_jobs = 0;
     uint32_t max_pieces = 0, light_images = 0;
     constexpr size_t PINNED_SPAN_GAP_MAX = 4096u;  // (bytes; below one page: see where the spans are built)
@@ -1255,6 +1266,13 @@ int jpgpu::batch_device_entropy_launch(jpgpu_batch *b, const DeviceEntropyImage 
                 uint32_t block_h[4] = {0, 0, 0, 0};
                 for (uint32_t c = 0; c < ps.ncomp; c++) block_h[c] = desc.components[ps.comp[c].frame_index].block_height;
                 if (!huff_scan_covers_planes(*sj, block_h)) needs_zeros = true;
+                // (only where the scan's MCU rows are the frame's: one interleaved scan of all components that covers the planes)
+                if (const WindowGeom *kg = win_geom.empty() ? nullptr : win_geom[img]; kg && images[k].scans->size() == 1 && !needs_zeros && ps.ncomp == desc.ncomp &&
+                                                                                  desc.ncomp > 1u && sj->cols == kg->mcu_w && sj->n_mcu == kg->mcu_w * kg->mcu_h) {
+                    bool same = true;
+                    for (uint32_t c = 0; c < ps.ncomp; c++) same = same && ps.comp[c].frame_index == c && ps.comp[c].h == kg->h[c] && ps.comp[c].v == kg->v[c];
+                    if (same) window_kept_mcu_rows(*kg, sj->keep_my0, sj->keep_my1);
+                }
                 // Entry-list pixel path: the image's ONE scan holds its three components interleaved in frame order, 2x2 / 1x1 / 1x1, with
                 // tables of their own for luma and chroma (the entries then carry their component), with or without restart segments, and
                 // covers the planes of the 4:2:0 walk the image belongs to.
@@ -1789,6 +1807,121 @@ bool jpgpu::batch_progressive_kernel_ms(jpgpu_batch *b, float *ms) {
     }
     return true;
 }
+
+// What jpgpu_batch_create_windowed would make of window `wn` on an image of descriptor `d`, without a batch: JPGPU_OK with
+// `windowed` (false: an empty window or one that covers the output grid — no window) and the output grid in gw x gh;
+// JPGPU_ERR_FORMAT for a window outside the grid, JPGPU_ERR_UNSUPPORTED for a descriptor the window planner refuses (`why`).
+// The pipeline sorts such images out per image before it forms sub-batches (a batch fails creation as a whole).
+int jpgpu::batch_check_window(const jpgpu_image_desc &d, const jpgpu_window &wn, bool &windowed, uint32_t &gw, uint32_t &gh, std::string &why) {
+    windowed = false;
+    window_grid(d.components, d.ncomp, d.out_w, d.out_h, gw, gh);
+    if (wn.w == 0 || wn.h == 0) return JPGPU_OK;
+    char msg[200];
+    if ((uint32_t)wn.x + wn.w > gw || (uint32_t)wn.y + wn.h > gh) {
+        snprintf(msg, sizeof(msg), "window (%u, %u) %ux%u outside the %ux%u image", wn.x, wn.y, wn.w, wn.h, gw, gh);
+        why = msg;
+        return JPGPU_ERR_FORMAT;
+    }
+    if (wn.x == 0 && wn.y == 0 && wn.w == gw && wn.h == gh) return JPGPU_OK;
+    uint8_t *dummy[4] = {nullptr, nullptr, nullptr, nullptr};
+    ImageJob ij;
+    size_t out_len = 0;
+    int rc = build_image_job(d.components, d.ncomp, dummy, d.out_w, d.out_h, d.color_transform, nullptr, ij, out_len, why);
+    if (rc) return rc;
+    WindowGeom wg;
+    const char *reason = "";
+    if (!window_geom_from_job(d.components, d.ncomp, ij, wn.x, wn.y, wn.w, wn.h, wg, reason)) {
+        snprintf(msg, sizeof(msg), "no window kernel for this descriptor: %s", reason);
+        why = msg;
+        return JPGPU_ERR_UNSUPPORTED;
+    }
+    windowed = true;
+    return JPGPU_OK;
+}
+// Other windows for the SAME window group (the pipeline's kept sub-batches; the batch must be idle): only the group's geometry, the
+// output offsets / sizes and the job tables depend on the windows — the coefficient arena, the fused plans' membership and every
+// staging block stay.  JPGPU_ERR_UNSUPPORTED, with nothing changed, when another set of images would be windowed (or the buffers
+// are the caller's): the caller creates a new batch then.  An image of the group whose new window covers its whole output stays in it.  The output arena grows when the new windows need more than it holds.
+int jpgpu::batch_rewindow(jpgpu_batch *b, const jpgpu_window *windows) {
+    if (!b || !windows) return JPGPU_ERR_FORMAT;
+    if (!b->own_out || b->win_ids.empty()) return JPGPU_ERR_UNSUPPORTED;
+    const uint32_t n = (uint32_t)b->descs.size();
+    std::vector<WindowGeom> geoms(b->win_ids.size());
+    std::vector<jpgpu_window> eff(n, jpgpu_window{0, 0, 0, 0});  // members: the window they decode
+    size_t k = 0;
+    for (uint32_t i = 0; i < n; i++) {
+        const jpgpu_image_desc &d = b->descs[i];
+        jpgpu_window wn = windows[i];
+        uint32_t gw = 0, gh = 0;
+        window_grid(d.components, d.ncomp, d.out_w, d.out_h, gw, gh);
+        const bool member = k < b->win_ids.size() && b->win_ids[k] == i;
+        const bool inside = wn.w != 0 && wn.h != 0 && (uint32_t)wn.x + wn.w <= gw && (uint32_t)wn.y + wn.h <= gh;
+        const bool windowed = inside && !(wn.x == 0 && wn.y == 0 && wn.w == gw && wn.h == gh);
+        if ((wn.w != 0 && wn.h != 0 && !inside) || (windowed && !member)) return JPGPU_ERR_UNSUPPORTED;
+        if (!member) continue;
+        // (a member whose new window is the whole image — one in a thousand of a loader's random crops — stays in the group: the window
+        // kernel decodes the whole grid to the same bytes, and the sub-batch need not be created anew for it)
+        if (!windowed) wn = jpgpu_window{0, 0, (uint16_t)gw, (uint16_t)gh};
+        eff[i] = wn;
+        uint8_t *dummy[4] = {nullptr, nullptr, nullptr, nullptr};
+        ImageJob ij;
+        size_t out_len = 0;
+        std::string err;
+        const char *why = "";
+        if (build_image_job(d.components, d.ncomp, dummy, d.out_w, d.out_h, d.color_transform, nullptr, ij, out_len, err) != JPGPU_OK ||
+            !window_geom_from_job(d.components, d.ncomp, ij, wn.x, wn.y, wn.w, wn.h, geoms[k], why))
+            return JPGPU_ERR_UNSUPPORTED;
+        geoms[k].first_plane_job = b->win_geoms[k].first_plane_job;
+        k++;
+    }
+    int rc = use_device(b->device, b->err);
+    if (rc) return rc;
+    size_t oo = 0, full = 0;
+    k = 0;
+    for (uint32_t i = 0; i < n; i++) {
+        const bool member = k < b->win_ids.size() && b->win_ids[k] == i;
+        if (member) k++;
+        const size_t len = member ? (size_t)eff[i].w * eff[i].h * b->descs[i].ncomp : b->out_full_len[i];
+        b->out_off[i] = oo;
+        b->out_len[i] = len;
+        oo += align_up(len, 256);
+        full += align_up(b->out_full_len[i], 256);
+    }
+    b->out_bytes = std::max<size_t>(oo, 256);
+    b->jobs_dirty = true;  // (every job's output pointer, the fused plans' included)
+    if (b->out_bytes > b->out_cap) {
+        B_HIP(hipDeviceSynchronize());
+        if (b->d_out) (void)hipFree(b->d_out);
+        b->d_out = nullptr;
+        b->out_cap = 0;
+        // (a quarter more than asked for, at most what the whole images take: the totals of a loader's random crops differ little from call to call)
+        const size_t cap = std::max(b->out_bytes, std::min(std::max<size_t>(full, 256), b->out_bytes + b->out_bytes / 4));
+        B_HIP(hipMalloc((void **)&b->d_out, cap));
+        b->out_cap = cap;
+    }
+    b->win_geoms = geoms;
+    b->w_max_tiles_x = b->w_max_bands = b->w_lds_bytes = 0;
+    for (bool &s : b->w_scales) s = false;
+    for (const WindowGeom &wg : b->win_geoms) {
+        b->w_max_tiles_x = std::max(b->w_max_tiles_x, wg.tiles_x);
+        b->w_max_bands = std::max(b->w_max_bands, wg.bands);
+        b->w_lds_bytes = std::max(b->w_lds_bytes, wg.lds_bytes);
+        b->w_scales[wg.scale] = true;
+    }
+    B_HIP(hipMemcpy(b->d_win_geoms, b->win_geoms.data(), b->win_geoms.size() * sizeof(WindowGeom), hipMemcpyHostToDevice));
+    return JPGPU_OK;
+}
+// bytes the output arena of the batch would hold without any window (what a pinned copy of it never needs more than)
+size_t jpgpu::batch_out_arena_bound(const jpgpu_batch *b) {
+    size_t full = 0;
+    if (b)
+        for (size_t v : b->out_full_len) full += align_up(v, 256);
+    return std::max<size_t>(full, 256);
+}
+bool jpgpu::batch_image_windowed(const jpgpu_batch *b, uint32_t image) {
+    return b && std::binary_search(b->win_ids.begin(), b->win_ids.end(), image);  // (win_ids is filled in image order)
+}
+uint32_t jpgpu::batch_windowed_images(const jpgpu_batch *b) { return b ? (uint32_t)b->win_ids.size() : 0u; }
 
 int jpgpu::batch_device_entropy_collect(jpgpu_batch *b, uint32_t *status, uint32_t n) {
     if (!b || !status || n != b->entropy_images.size()) return JPGPU_ERR_FORMAT;

@@ -188,7 +188,68 @@ struct jpgpu_decoder {
     std::vector<uint8_t> icc;
     CoefSink coefs;
     bool coefs_done = false;
+    jpgpu_window win{0, 0, 0, 0};  // jpgpu_decoder_set_window (w or h 0: the whole image)
 };
+
+// The window decode() is to honour, checked against the output grid in force now (after scale): false when there is none (not
+// set, or it covers the whole output); throws JPGPU_ERR_FORMAT for one that does not lie inside.  The frame header must be read.
+static bool window_in_force(const jpgpu_decoder *d) {
+    if (d->win.w == 0 || d->win.h == 0) return false;
+    const Frontend &fe = *d->fe;
+    const uint32_t gw = fe.ncomp() == 1 ? fe.components()[0].size_width : fe.output_width();
+    const uint32_t gh = fe.ncomp() == 1 ? fe.components()[0].size_height : fe.output_height();
+    if ((uint32_t)d->win.x + d->win.w > gw || (uint32_t)d->win.y + d->win.h > gh) {
+        char msg[160];
+        snprintf(msg, sizeof(msg), "window (%u, %u) %ux%u outside the %ux%u image", d->win.x, d->win.y, d->win.w, d->win.h, gw, gh);
+        throw DecodeError{JPGPU_ERR_FORMAT, msg};
+    }
+    return !(d->win.x == 0 && d->win.y == 0 && d->win.w == gw && d->win.h == gh);
+}
+
+// The Worker route with a window: the coefficients the front-end retained (`cs`, by frame component; rows a scan never reached
+// stay zero, like the Worker's zero-initialised plane) go through a one-image windowed batch in place of jpgpu_compute_image.
+static void decode_window_from_coefficients(jpgpu_decoder *d, const CoefSink &cs) {
+    const Frontend &fe = *d->fe;
+    jpgpu_image_desc desc;
+    memset(&desc, 0, sizeof(desc));
+    desc.ncomp = fe.ncomp();
+    for (uint32_t c = 0; c < desc.ncomp; c++) {
+        desc.components[c] = fe.components()[c];
+        memcpy(desc.quantization_tables[c], fe.qtable_of_component(c), 128);
+    }
+    desc.out_w = fe.output_width();
+    desc.out_h = fe.output_height();
+    desc.color_transform = fe.color_transform();
+    struct BatchHold {  // (destroyed on every path out)
+        jpgpu_batch *b = nullptr;
+        ~BatchHold() {
+            if (b) jpgpu_batch_destroy(b);
+        }
+    } hold;
+    auto check = [&](int rc) {
+        if (rc) throw DecodeError{rc, hold.b ? jpgpu_batch_last_error(hold.b) : "jpgpu_batch_create_windowed"};
+    };
+    check(jpgpu_batch_create_windowed(d->device, &desc, &d->win, 1, JPGPU_BATCH_DEFAULT, &hold.b));
+    std::vector<int16_t> padded;
+    for (uint32_t c = 0; c < desc.ncomp; c++) {
+        const size_t need = jpgpu_batch_coef_bytes(hold.b, 0, c) / sizeof(int16_t);
+        const std::vector<int16_t> &have = cs.frame[c];
+        if (have.empty()) throw DecodeError{JPGPU_ERR_FORMAT, "not all components have data"};
+        const int16_t *src = have.data();
+        if (have.size() != need) {  // (a scan that ended early, or rows past the plane)
+            padded.assign(need, 0);
+            memcpy(padded.data(), have.data(), std::min(need, have.size()) * sizeof(int16_t));
+            src = padded.data();
+        }
+        check(jpgpu_batch_upload(hold.b, 0, c, src, need));
+    }
+    check(jpgpu_batch_decode(hold.b, nullptr));
+    check(jpgpu_batch_synchronize(hold.b, nullptr));
+    d->pixels.resize(std::max<size_t>(jpgpu_batch_out_bytes(hold.b, 0), 1));
+    size_t got = 0;
+    check(jpgpu_batch_download(hold.b, 0, d->pixels.data(), d->pixels.size(), &got));
+    d->pixels.resize(got);
+}
 
 static int fail(jpgpu_decoder *d, const DecodeError &e) {
     d->err = e.message;
@@ -286,7 +347,14 @@ size_t jpgpu_decoder_output_bytes(const jpgpu_decoder *d) {
     if (!d || !d->fe->has_frame()) return 0;
     const jpgpu_image_info i = d->fe->info();
     const size_t bpp = i.pixel_format == JPGPU_PIXEL_L8 ? 1 : i.pixel_format == JPGPU_PIXEL_L16 ? 2 : i.pixel_format == JPGPU_PIXEL_RGB24 ? 3 : 4;
+    if (d->win.w != 0 && d->win.h != 0) return (size_t)d->win.w * d->win.h * bpp;  // (what decode() returns if it honours the window)
     return (size_t)i.width * i.height * bpp;
+}
+
+int jpgpu_decoder_set_window(jpgpu_decoder *d, uint16_t x, uint16_t y, uint16_t w, uint16_t h) {
+    if (!d) return JPGPU_ERR_FORMAT;
+    d->win = (w == 0 || h == 0) ? jpgpu_window{0, 0, 0, 0} : jpgpu_window{x, y, w, h};
+    return JPGPU_OK;
 }
 
 int jpgpu_decoder_decode(jpgpu_decoder *d, uint8_t *dst, size_t cap, size_t *len) {
@@ -297,6 +365,15 @@ int jpgpu_decoder_decode(jpgpu_decoder *d, uint8_t *dst, size_t cap, size_t *len
         std::unique_ptr<Frontend> nf(new Frontend(bytes, n));
         d->fe = std::move(nf);
         d->fe_spent = false;
+    }
+    bool windowed = false;
+    if (!d->decoded && d->win.w != 0 && d->win.h != 0) {  // a window outside the output: nothing is decoded
+        try {
+            d->fe->read_info();
+            windowed = window_in_force(d);
+        } catch (const DecodeError &e) {
+            return fail(d, e);
+        }
     }
     if (!d->decoded && d->device >= 0 && !d->customized && !getenv("JPGPU_DECODER_NO_DEVICE_ENTROPY")) {
         // same pixels, other route: see kDeviceEntropyMinPixels.  Anything the planner or the device decoder does not
@@ -316,7 +393,7 @@ int jpgpu_decoder_decode(jpgpu_decoder *d, uint8_t *dst, size_t cap, size_t *len
                     jpgpu_pipeline *p = pipeline_pool().take(d->device);
                     if (!p && jpgpu_pipeline_create(d->device, 2, &p) != JPGPU_OK) p = nullptr;
                     if (p) {
-                        if (jpgpu_pipeline_decode(p, &bytes, &n, 1, JPGPU_PIPELINE_DOWNLOAD | JPGPU_PIPELINE_DEVICE_ENTROPY) == JPGPU_OK &&
+                        if (jpgpu_pipeline_decode_windowed(p, &bytes, &n, windowed ? &d->win : nullptr, 1, JPGPU_PIPELINE_DOWNLOAD | JPGPU_PIPELINE_DEVICE_ENTROPY) == JPGPU_OK &&
                             jpgpu_pipeline_image_status(p, 0) == JPGPU_OK) {
                             const size_t nb = jpgpu_pipeline_pixel_bytes(p, 0);
                             const uint8_t *px = jpgpu_pipeline_pixels_host(p, 0);
@@ -353,8 +430,8 @@ int jpgpu_decoder_decode(jpgpu_decoder *d, uint8_t *dst, size_t cap, size_t *len
         try {
             if (d->device < 0) throw DecodeError{JPGPU_ERR_NO_DEVICE, "decoder was created without a device (host-only)"};
             slot.take();
-            if (!d->worker) d->worker = worker_pool().take(d->device);
-            if (!d->worker) {
+            if (!windowed && !d->worker) d->worker = worker_pool().take(d->device);
+            if (!windowed && !d->worker) {
                 int rc = jpgpu_worker_create(d->device, &d->worker);
                 if (rc) throw DecodeError{rc, "no usable MI355X device: the pixel pipeline has no CPU fallback"};
             }
@@ -382,6 +459,19 @@ int jpgpu_decoder_decode(jpgpu_decoder *d, uint8_t *dst, size_t cap, size_t *len
             const bool trace = getenv("JPGPU_DECODER_TRACE") != nullptr;
             const auto t0 = std::chrono::steady_clock::now();
             auto ms_since = [&](std::chrono::steady_clock::time_point a) { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - a).count(); };
+            if (windowed) {  // coefficients retained on the host -> a one-image windowed batch (no worker is borrowed)
+                CoefSink kept;
+                d->fe->decode_to(kept);
+                decode_window_from_coefficients(d, kept);
+                d->decoded = true;
+                if (len) *len = d->pixels.size();
+                if (!dst || cap < d->pixels.size()) {
+                    d->err = "decode: destination too small";
+                    return JPGPU_ERR_FORMAT;
+                }
+                if (!d->pixels.empty()) memcpy(dst, d->pixels.data(), d->pixels.size());
+                return JPGPU_OK;
+            }
             GpuSink sink(d->worker);
             d->fe->decode_to(sink);
             const double t_decode = ms_since(t0);

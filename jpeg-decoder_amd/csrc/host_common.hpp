@@ -49,6 +49,15 @@ int batch_upload_compact(jpgpu_batch *b, uint32_t image, uint32_t comp, const vo
 // mapped block itself (huff.hip, launch_copy_to_host); falls back to the copy engine if the block has no device mapping
 int copy_device_to_pinned_host(void *host_pinned, const void *d_src, size_t bytes, void *hip_stream);
 
+// Windows per image ahead of jpgpu_batch_create_windowed (batch.cpp): is `wn` a window on `d` (windowed), no window (empty, or the
+// whole gw x gh output grid), outside the grid (JPGPU_ERR_FORMAT) or refused by the window planner (JPGPU_ERR_UNSUPPORTED)?
+int batch_check_window(const jpgpu_image_desc &d, const jpgpu_window &wn, bool &windowed, uint32_t &gw, uint32_t &gh, std::string &why);
+uint32_t batch_windowed_images(const jpgpu_batch *b);  // images of the batch in the window group
+bool batch_image_windowed(const jpgpu_batch *b, uint32_t image);  // ... is this one of them (its pixels come from the window kernel)
+// other windows for the same window group of an idle batch, in place (batch.cpp); JPGPU_ERR_UNSUPPORTED: create a new batch instead
+int batch_rewindow(jpgpu_batch *b, const jpgpu_window *windows);
+size_t batch_out_arena_bound(const jpgpu_batch *b);  // jpgpu_batch_out_arena_bytes of the same images without windows
+
 // before a worker goes back to the decoder API's pool of idle workers
 void worker_recycle(jpgpu_worker *w);
 
@@ -83,7 +92,9 @@ struct DeviceScratch {
 // either, the copy engine reads them.  n_light (optional): how many of the listed images took that route.
 // | DEVICE_ENTROPY_ENTRY_PIXELS — 4:2:0 images whose scan qualifies keep their entry lists and the next jpgpu_batch_decode on the same
 // stream runs the walk that reads them (fused_entries.hpp): nothing of such an image goes through the coefficient arena.
-constexpr uint32_t DEVICE_ENTROPY_LIGHT = 1u, DEVICE_ENTROPY_INPUT_PINNED = 2u, DEVICE_ENTROPY_ENTRY_PIXELS = 4u;
+// | DEVICE_ENTROPY_WINDOW_ROWS — images of the batch's window group: the expansion stores only the blocks of the MCU rows their window
+// kernel reads (HuffSyncJob::keep_my0 / keep_my1); without it every block of the scan, as for all other images.
+constexpr uint32_t DEVICE_ENTROPY_LIGHT = 1u, DEVICE_ENTROPY_INPUT_PINNED = 2u, DEVICE_ENTROPY_ENTRY_PIXELS = 4u, DEVICE_ENTROPY_WINDOW_ROWS = 8u;
 int batch_device_entropy_launch(jpgpu_batch *b, const DeviceEntropyImage *images, uint32_t n, void *hip_stream,
                                 const std::function<void(uint32_t, const std::function<void(uint32_t)> &)> *par = nullptr,
                                 void *copy_stream = nullptr, DeviceScratch *scratch = nullptr, bool alone = false, uint32_t mode = 0u,

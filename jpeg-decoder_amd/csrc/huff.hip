@@ -540,11 +540,15 @@ static_assert(sizeof(HuffSyncJob) % 4 == 0, "copied by dwords");
 struct ExpandAt {
     uint32_t inv_bpm, inv_cols;
     uint32_t bpm, cols, q0, mx0, my0;  // block S = block q0 of MCU (mx0, my0)
+    uint32_t keep_lo, keep_n;          // MCU rows whose blocks are stored: [keep_lo, keep_lo + keep_n) (HuffSyncJob::keep_my0 / keep_my1; all: 0, 2^32 - 1)
 };
 __device__ __forceinline__ uint32_t small_div(uint32_t n, uint32_t x, uint32_t inv) { return x == 1u ? n : __umulhi(n, inv); }
 __device__ __forceinline__ uint32_t rfl(uint32_t v) { return (uint32_t)__builtin_amdgcn_readfirstlane((int)v); }
 
-// slots [s_first, s_first + n) of the wave's ring hold blocks S + d0 .. S + d0 + n - 1: written out and cleared, eight lanes per block
+// slots [s_first, s_first + n) of the wave's ring hold blocks S + d0 .. S + d0 + n - 1: written out and cleared, eight lanes per block.
+// A block of an MCU row outside the rows kept (windowed images) is not stored: a whole 128-byte line less, decided per group of eight
+// lanes; UNIFORM scans still store its DC word (two bytes, one lane) for the sums of huff_dc_prefix_kernel.
+template <bool UNIFORM>
 __device__ __forceinline__ void expand_store_blocks(JP_LDS ExpandLds &E, JP_LDS uint16_t *ring, const ExpandAt &at, uint32_t S, uint32_t d0, uint32_t n,
                                                     uint32_t total) {
     const uint32_t lane = threadIdx.x & 63u, sub = lane & 7u, grp = lane >> 3;
@@ -559,7 +563,8 @@ __device__ __forceinline__ void expand_store_blocks(JP_LDS ExpandLds &E, JP_LDS 
                 const uint32_t t = at.q0 + d0 + s, dm = small_div(t, at.bpm, at.inv_bpm), q = (t - dm * at.bpm) & 15u;
                 const uint32_t x = at.mx0 + dm, dy = small_div(x, at.cols, at.inv_cols), mx = x - dy * at.cols, my = at.my0 + dy;
                 const uint64_t dst = E.q_dst[q].base + (uint64_t)my * E.q_dst[q].row_stride + (uint64_t)mx * E.q_dst[q].mcu_stride;
-                ((JP_GLOBAL v4u *)(uintptr_t)dst)[sub] = v4u{a.x, a.y, b.x, b.y};
+                if (my - at.keep_lo < at.keep_n) ((JP_GLOBAL v4u *)(uintptr_t)dst)[sub] = v4u{a.x, a.y, b.x, b.y};
+                else if (UNIFORM && sub == 0u) *(JP_GLOBAL uint16_t *)(uintptr_t)dst = (uint16_t)a.x;
             }
         }
     }
@@ -660,7 +665,7 @@ __device__ __forceinline__ void expand_chunk(JP_LDS ExpandLds &E, JP_LDS uint16_
             if (pending >= EXP_THR) {
                 const uint32_t out = EXP_THR >= 8u ? pending & ~7u : pending, keep = pending - out + 1u;  // the rest, and the open block, move to the front
                 __builtin_amdgcn_wave_barrier();
-                expand_store_blocks(E, ring, at, S, base, out, total);
+                expand_store_blocks<UNIFORM>(E, ring, at, S, base, out, total);
                 if ((lane >> 3) < keep) {
                     JP_LDS v2u *from = (JP_LDS v2u *)(ring + (out + (lane >> 3)) * EXP_SLOT + (lane & 7u) * 8u), *to = (JP_LDS v2u *)(ring + lane * 8u + (lane >> 3) * (EXP_SLOT - 64u));
                     const v2u x = from[0], y = from[1];
@@ -684,7 +689,7 @@ __device__ __forceinline__ void expand_chunk(JP_LDS ExpandLds &E, JP_LDS uint16_
         if (leadj < cntj) break;  // a block starts in chunk j: ours ended there
     }
     __builtin_amdgcn_wave_barrier();
-    expand_store_blocks(E, ring, at, S, base, started - base, total);
+    expand_store_blocks<UNIFORM>(E, ring, at, S, base, started - base, total);
     __builtin_amdgcn_wave_barrier();
 }
 
@@ -716,6 +721,8 @@ __global__ __launch_bounds__(EXP_WAVES * 64) void huff_expand_kernel(const HuffS
     at.inv_bpm = bpm > 1u ? 0xffffffffu / bpm + 1u : 0u;
     at.inv_cols = cols > 1u ? 0xffffffffu / cols + 1u : 0u;
     at.q0 = at.mx0 = at.my0 = 0u;
+    at.keep_lo = rfl(job.keep_my0);
+    at.keep_n = rfl(job.keep_my1) ? rfl(job.keep_my1) - at.keep_lo : 0xffffffffu;
     uint32_t rg_dc = 0, rg_ac = 0;
     // lanes 0 .. EXP_CHUNKS - 1 fetch what the wave has to know of its chunks (one wait for all of them) ...
     const uint32_t i0 = first_chunk + wave * EXP_CHUNKS;

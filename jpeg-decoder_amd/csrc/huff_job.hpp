@@ -172,6 +172,11 @@ struct HuffSyncJob {             // one scan of one image, for either device dec
     const uint32_t *weave;  // huff_weave_dwords(n_chunks, chunk_shift) dwords
     uint32_t data_dwords;   // dwords that may be read from `data` (the scan's slots); what lies beyond counts as zeros
     uint32_t keep_lists;    // 1: the pixel kernel reads the entry lists itself (fused_entries.hpp) — no expansion into the arena
+    // Windowed images (window_band.hpp): the window kernel reads only the MCU rows [keep_my0, keep_my1) of the scan (the window's MCU
+    // rectangle and its rings, window_kept_mcu_rows), so huff_expand_kernel stores only the blocks of those rows — of a block outside
+    // them nothing (its 128 bytes keep what they held; nobody reads them), or, in a `uniform` scan, its DC word alone (huff_dc_prefix_kernel
+    // sums the DC differences over ALL blocks of the plane).  keep_my1 == 0: every row (all other images).
+    uint32_t keep_my0, keep_my1;
 };
 // Where chunk i lies: bits [start, end) of the job's data, whether a segment starts there, which segment it belongs to.
 struct HuffChunkSpan {

@@ -254,6 +254,7 @@ struct SubBatch {
     size_t h_coef_bytes = 0, h_out_bytes = 0;
     bool compact = false;             // layout of h_coef: compact regions (stage_off) or a mirror of the arena
     std::vector<size_t> stage_off;    // compact mode: [image*4 + comp] offset of the component's region in h_coef
+    std::vector<jpgpu_window> wins;   // the window of every image as the batch was created with it (w == 0: none); empty: no image has one
     uint32_t remaining = 0;  // images not yet uploaded / failed (uploader thread only)
     hipEvent_t ready[kCopyStreams] = {nullptr, nullptr, nullptr, nullptr};
     hipEvent_t decoded = nullptr;  // recorded on the compute stream behind the sub-batch's pixel kernels: downloads and the gather wait for it
@@ -266,6 +267,7 @@ struct SubBatch {
         h_coef_bytes = h_out_bytes = 0;
         descs.clear();
         stage_off.clear();
+        wins.clear();
     }
 };
 
@@ -291,6 +293,7 @@ struct jpgpu_pipeline {
     std::vector<int> status;
     std::vector<std::string> errors;
     std::vector<jpgpu_image_info> infos;
+    std::vector<jpgpu_window> wins;  // per image: the window decoded (jpgpu_pipeline_image_window; the whole output grid when there was none)
     std::vector<int32_t> sub_of, slot;  // image -> sub-batch / index in it, -1 if it never got there
     std::vector<std::vector<jpgpu::host::PlannedScan>> plans;  // per image: scans for the device entropy decoder (empty: host)
     std::vector<jpgpu::host::ProgPlan> prog_plans;             // per image: the scans of a PROGRESSIVE frame for the device (no scans: host)
@@ -336,7 +339,7 @@ static const jpgpu_pipeline *child_of(const jpgpu_pipeline *p, uint32_t &image) 
     image /= n;
     return c;
 }
-static int multi_decode(jpgpu_pipeline *p, const uint8_t *const *data, const size_t *len, uint32_t n, uint32_t flags);
+static int multi_decode(jpgpu_pipeline *p, const uint8_t *const *data, const size_t *len, const jpgpu_window *windows, uint32_t n, uint32_t flags);
 // Up to how many scans does a call walk its progressive frames a WAVE per scan (pipelined, huff_prog_job.hpp)?  Always: the launch
 // order keeps a frame's waves on one XCD, producers in front (csrc/batch.cpp), so an oversubscribed launch cannot starve a producer
 // (round 5's lanes had to fit the device at once).  Beyond the limit: a wave per TRACK, its scans one after the other —
@@ -604,13 +607,18 @@ static uint32_t progressive_share_for_the_device(jpgpu_pipeline *p, const uint8_
 }
 
 int jpgpu_pipeline_decode(jpgpu_pipeline *p, const uint8_t *const *data, const size_t *len, uint32_t n, uint32_t flags) {
+    return jpgpu_pipeline_decode_windowed(p, data, len, nullptr, n, flags);
+}
+
+int jpgpu_pipeline_decode_windowed(jpgpu_pipeline *p, const uint8_t *const *data, const size_t *len, const jpgpu_window *windows, uint32_t n,
+                                   uint32_t flags) {
     jpgpu::TraceRange roctx_range("jpgpu_pipeline_decode");
     // (unknown bits are refused, not ignored: 8u was round 2-3's JPGPU_PIPELINE_PROGRESSIVE_DELTAS, removed in round 4 — a caller built
     // against that header would otherwise silently get another transport: ADVICE r4)
     constexpr uint32_t kKnownFlags = JPGPU_PIPELINE_DOWNLOAD | JPGPU_PIPELINE_DENSE | JPGPU_PIPELINE_DEVICE_ENTROPY | JPGPU_PIPELINE_GATHER |
                                      JPGPU_PIPELINE_HOST_LIGHT | JPGPU_PIPELINE_HOST_STAGED | JPGPU_PIPELINE_INPUT_PINNED | JPGPU_PIPELINE_PROGRESSIVE_ON_HOST;
     if (p && (flags & ~kKnownFlags)) return jpgpu::set_err(p->err, JPGPU_ERR_FORMAT, "jpgpu_pipeline_decode: unknown flag bits 0x%x (this library: %s)", flags & ~kKnownFlags, jpgpu_version());
-    if (p && !p->children.empty()) return (n && (!data || !len)) ? JPGPU_ERR_FORMAT : multi_decode(p, data, len, n, flags);
+    if (p && !p->children.empty()) return (n && (!data || !len)) ? JPGPU_ERR_FORMAT : multi_decode(p, data, len, windows, n, flags);
     if (!p || !p->pool || (n && (!data || !len))) return JPGPU_ERR_FORMAT;
     if ((flags & JPGPU_PIPELINE_GATHER) && !p->gather_on) flags &= ~(uint32_t)JPGPU_PIPELINE_GATHER;  // (one device: the pixels are where a gather would put them)
     int rc = jpgpu::use_device(p->device, p->err);
@@ -626,6 +634,7 @@ int jpgpu_pipeline_decode(jpgpu_pipeline *p, const uint8_t *const *data, const s
     p->status.assign(n, JPGPU_ERR_INTERNAL);
     p->errors.assign(n, std::string());
     p->infos.assign(n, jpgpu_image_info{});
+    p->wins.assign(n, jpgpu_window{0, 0, 0, 0});
     p->sub_of.assign(n, -1);
     p->plans.clear();
     p->plans.resize(n);
@@ -638,6 +647,10 @@ int jpgpu_pipeline_decode(jpgpu_pipeline *p, const uint8_t *const *data, const s
     p->t = jpgpu_pipeline_timings{};
     p->t.threads = p->pool->size() + p->stage_pool->size();  // (+ one uploader thread per call, which mostly waits)
     std::vector<jpgpu_image_desc> cand(n);
+    // Windows (jpgpu_pipeline_decode_windowed) are checked per image as soon as its header gives the output grid, before anything is
+    // dealt to sub-batches — a batch refuses a bad window for all of its images, here only the image concerned fails and leaves the
+    // call as an image whose header failed does.  win[i].w != 0 afterwards: image i runs the window kernel.
+    std::vector<jpgpu_window> win(windows ? n : 0u, jpgpu_window{0, 0, 0, 0});
 
     // 1. headers
     p->pool->run(n, [&](uint32_t i) {
@@ -697,6 +710,15 @@ int jpgpu_pipeline_decode(jpgpu_pipeline *p, const uint8_t *const *data, const s
                 }
             }
             cand[i] = d;
+            {
+                uint32_t gw = 0, gh = 0;
+                bool windowed = false;
+                std::string why;
+                const int v = jpgpu::batch_check_window(d, windows ? windows[i] : jpgpu_window{0, 0, 0, 0}, windowed, gw, gh, why);
+                if (v != JPGPU_OK) throw DecodeError{v, why};
+                p->wins[i] = jpgpu_window{0, 0, (uint16_t)gw, (uint16_t)gh};
+                if (windowed) win[i] = p->wins[i] = windows[i];
+            }
             if (device_entropy && p->infos[i].coding_process == JPGPU_CODING_DCT_PROGRESSIVE) {
                 // a progressive frame: its scans as tracks for the device (huff_prog_wave.hpp), if the stream is plainly eligible;
                 // how many of a call's eligible frames really go there is decided below, once all headers are read
@@ -733,6 +755,8 @@ int jpgpu_pipeline_decode(jpgpu_pipeline *p, const uint8_t *const *data, const s
             p->errors[i] = e.what();
         }
     });
+    bool any_window = false;
+    for (uint32_t i = 0; i < n && windows && !any_window; i++) any_window = p->status[i] == JPGPU_OK && win[i].w != 0;
     if (device_entropy) keep_on_host_what_the_device_would_decode_slower(p, data, len, n);
     const uint32_t n_prog_dev = device_progressive ? progressive_share_for_the_device(p, data, len, n) : 0u;
     const double t1 = now_ms();
@@ -793,10 +817,14 @@ int jpgpu_pipeline_decode(jpgpu_pipeline *p, const uint8_t *const *data, const s
         SubBatch &sb = p->subs[j];
         const uint32_t first = bounds[j], last = bounds[j + 1];
         std::vector<jpgpu_image_desc> descs;
+        std::vector<jpgpu_window> wins;  // (stays empty when no image of the sub-batch has a window: jpgpu_batch_create's own path)
+        bool sub_windowed = false;
+        for (uint32_t k = first; any_window && k < last; k++) sub_windowed = sub_windowed || win[ok[k]].w != 0;
         for (uint32_t k = first; k < last; k++) {
             p->sub_of[ok[k]] = (int32_t)j;
             p->slot[ok[k]] = (int32_t)(k - first);
             descs.push_back(cand[ok[k]]);
+            if (sub_windowed) wins.push_back(win[ok[k]]);
         }
         sb.remaining = last - first;
         // Sub-batches of device-entropy images need no pinned staging for coefficients (their entropy-coded bytes are staged by
@@ -805,9 +833,22 @@ int jpgpu_pipeline_decode(jpgpu_pipeline *p, const uint8_t *const *data, const s
         const bool staged = j >= n_dev_subs;
         bool reuse = sb.batch && descs.size() == sb.descs.size() && sb.compact == compact && (sb.h_coef != nullptr) == staged;
         for (size_t k = 0; reuse && k < descs.size(); k++) reuse = same_geometry(descs[k], sb.descs[k]);
+        // ... and the same windows: the window group's geometry and the output offsets are made from them (a kept batch with other
+        // windows would return the pixels of the old ones).  Other windows for the SAME set of windowed images — a loader's fresh
+        // random crops — are set in place (jpgpu::batch_rewindow: the arenas, plans and staging blocks stay; JPGPU_PIPE_REWINDOW=0, read
+        // per call: A/B); anything else is a new batch.
+        const double s0 = getenv("JPGPU_PIPE_TRACE") ? now_ms() : 0.0;
+        const char *how = reuse ? "kept" : "created";
+        if (reuse && !(wins.size() == sb.wins.size() && (wins.empty() || memcmp(wins.data(), sb.wins.data(), wins.size() * sizeof(jpgpu_window)) == 0))) {
+            const char *rw = getenv("JPGPU_PIPE_REWINDOW");
+            int rrc = JPGPU_ERR_UNSUPPORTED;
+            if (!wins.empty() && !sb.wins.empty() && !(rw && atoi(rw) == 0)) rrc = jpgpu::batch_rewindow(sb.batch, wins.data());
+            if (rrc == JPGPU_OK) sb.wins = wins, how = "re-windowed in place";
+            else reuse = false, how = "created (other windows)";
+        }
         if (!reuse) {
             sb.drop();
-            rc = jpgpu_batch_create(p->device, descs.data(), (uint32_t)descs.size(), JPGPU_BATCH_DEFAULT, &sb.batch);
+            rc = jpgpu_batch_create_windowed(p->device, descs.data(), wins.empty() ? nullptr : wins.data(), (uint32_t)descs.size(), JPGPU_BATCH_DEFAULT, &sb.batch);
             if (rc) {
                 // a frame the pixel backend refuses (e.g. an impossible sampling combination) fails the images of
                 // its sub-batch the way the reference fails it in compute_image
@@ -822,6 +863,7 @@ int jpgpu_pipeline_decode(jpgpu_pipeline *p, const uint8_t *const *data, const s
                 continue;
             }
             sb.descs = descs;
+            sb.wins = wins;
             sb.compact = compact;
             sb.h_coef_bytes = jpgpu_batch_coef_arena_bytes(sb.batch);
             if (compact) {  // worst-case compact size per component (12 B/block more than dense), 256-B aligned
@@ -837,10 +879,16 @@ int jpgpu_pipeline_decode(jpgpu_pipeline *p, const uint8_t *const *data, const s
             if (staged) P_HIP(hipHostMalloc((void **)&sb.h_coef, sb.h_coef_bytes, hipHostMallocDefault));
             else sb.h_coef_bytes = 0;
         }
-        if (download && !sb.h_out) {
-            sb.h_out_bytes = jpgpu_batch_out_arena_bytes(sb.batch);
+        if (download && (!sb.h_out || sb.h_out_bytes < jpgpu_batch_out_arena_bytes(sb.batch))) {
+            if (sb.h_out) (void)hipHostFree(sb.h_out);
+            sb.h_out = nullptr;
+            // (a sub-batch with windows: a quarter more than these windows need, at most what the whole images take — the totals of a
+            // loader's fresh random crops differ little from call to call, and pinning memory anew costs milliseconds)
+            const size_t need = jpgpu_batch_out_arena_bytes(sb.batch);
+            sb.h_out_bytes = sb.wins.empty() ? need : std::max(need, std::min(jpgpu::batch_out_arena_bound(sb.batch), need + need / 4));
             P_HIP(hipHostMalloc((void **)&sb.h_out, sb.h_out_bytes, hipHostMallocDefault));
         }
+        if (s0 != 0.0) fprintf(stderr, "pipeline trace: sub-batch %u (%zu images, %zu with a window): %s in %.2f ms\n", j, descs.size(), (size_t)jpgpu::batch_windowed_images(sb.batch), how, now_ms() - s0);
         const char *pth = jpgpu_batch_path(sb.batch);
         if (p->path.empty()) p->path = pth;
         else if (p->path != pth) p->path = "mixed";
@@ -904,8 +952,12 @@ int jpgpu_pipeline_decode(jpgpu_pipeline *p, const uint8_t *const *data, const s
     // (csrc/fused_entries.hpp) instead of whole blocks expanded into the coefficient arena; 0: round 5's expansion kernel for every image
     const char *entry_env = getenv("JPGPU_PIPE_ENTRY_PIXELS");  // (read per call: tests switch it)
     const bool entry_pixels = entry_env ? atoi(entry_env) != 0 : true;
+    // JPGPU_PIPE_WINDOW_ROWS (default 1): for windowed images the expansion stores only the blocks of the MCU rows their window reads
+    // (HuffSyncJob::keep_my0 / keep_my1, csrc/huff.hip); 0: every block of the scan, as for unwindowed images (A/B, tests)
+    const char *rows_env = getenv("JPGPU_PIPE_WINDOW_ROWS");  // (read per call)
+    const bool window_rows = rows_env ? atoi(rows_env) != 0 : true;
     const uint32_t entropy_mode = (host_light ? jpgpu::DEVICE_ENTROPY_LIGHT : 0u) | (input_pinned ? jpgpu::DEVICE_ENTROPY_INPUT_PINNED : 0u) |
-                                  (entry_pixels ? jpgpu::DEVICE_ENTROPY_ENTRY_PIXELS : 0u);
+                                  (entry_pixels ? jpgpu::DEVICE_ENTROPY_ENTRY_PIXELS : 0u) | (window_rows ? jpgpu::DEVICE_ENTROPY_WINDOW_ROWS : 0u);
     // Progressive frames for the device: a lane per scan only while ALL the call's lanes fit the device at once (prog_lanes_max())
     uint64_t prog_lanes = 0;
     for (uint32_t i = 0; i < n; i++)
@@ -939,9 +991,9 @@ int jpgpu_pipeline_decode(jpgpu_pipeline *p, const uint8_t *const *data, const s
             // (by a copy kernel that writes the pinned block itself: the copy engine's hipMemcpyAsync reached 33 GB/s in here — with a
             // host core busy the whole time — against 57 for the same copies alone: tools/attic/probe_d2h*.hip, profiles/round5)
             if (hipStreamWaitEvent(ds, sb.decoded, 0) != hipSuccess ||
-                jpgpu::copy_device_to_pinned_host(sb.h_out, jpgpu_batch_out_arena(sb.batch), sb.h_out_bytes, ds) != JPGPU_OK)
+                jpgpu::copy_device_to_pinned_host(sb.h_out, jpgpu_batch_out_arena(sb.batch), jpgpu_batch_out_arena_bytes(sb.batch), ds) != JPGPU_OK)
                 return false;
-            if (trace) fprintf(stderr, "pipeline trace: download of sub-batch %u (%zu MB) enqueued at +%.2f ms, the call took %.2f ms\n", sj, sb.h_out_bytes >> 20, c0 - t2, now_ms() - c0);
+            if (trace) fprintf(stderr, "pipeline trace: download of sub-batch %u (%zu MB) enqueued at +%.2f ms, the call took %.2f ms\n", sj, jpgpu_batch_out_arena_bytes(sb.batch) >> 20, c0 - t2, now_ms() - c0);
         }
         if (p->gather_on && p->d_gather) {
             const size_t bytes = jpgpu_batch_out_arena_bytes(sb.batch);
@@ -1212,10 +1264,11 @@ int jpgpu_pipeline_decode(jpgpu_pipeline *p, const uint8_t *const *data, const s
     // (a child's gather stream is NOT waited for here: the parent does, after every child has decoded — what it then still waits is the exposed part)
     const double t4 = now_ms();
     uint64_t pixel_bytes = 0;
-    uint32_t okc = 0;
+    uint32_t okc = 0, windowed_images = 0;
     for (uint32_t i = 0; i < n; i++)
         if (p->status[i] == JPGPU_OK) {
             okc++;
+            if (any_window && jpgpu::batch_image_windowed(p->subs[(uint32_t)p->sub_of[i]].batch, (uint32_t)p->slot[i])) windowed_images++;
             pixel_bytes += jpgpu_batch_out_bytes(p->subs[(uint32_t)p->sub_of[i]].batch, (uint32_t)p->slot[i]);
         }
     p->t.headers_ms = t1 - t0;
@@ -1239,6 +1292,7 @@ int jpgpu_pipeline_decode(jpgpu_pipeline *p, const uint8_t *const *data, const s
     p->t.images_device_progressive = device_prog_images;
     p->t.images_host_light = light_images;
     p->t.images_entry_pixels = entry_images;
+    p->t.images_windowed = windowed_images;
     p->t.input_pinned = input_pinned ? 1u : 0u;
     if (trace && (prog_host_bytes || device_prog_images))
         fprintf(stderr, "pipeline trace: progressive frames: %u on the device (walk %.2f ms, launches + range scan + pixels %.2f ms), %u on the host (entropy phase %.2f ms, %.1f ns per byte and thread)\n",
@@ -1274,6 +1328,12 @@ int jpgpu_pipeline_image_info(const jpgpu_pipeline *p, uint32_t i, jpgpu_image_i
     MULTI(p, i, jpgpu_pipeline_image_info(c, ci, info), JPGPU_ERR_FORMAT)
     if (!p || i >= p->n || !info || i >= p->has_frame.size() || !p->has_frame[i]) return JPGPU_ERR_FORMAT;
     *info = p->infos[i];
+    return JPGPU_OK;
+}
+int jpgpu_pipeline_image_window(const jpgpu_pipeline *p, uint32_t i, jpgpu_window *out) {
+    MULTI(p, i, jpgpu_pipeline_image_window(c, ci, out), JPGPU_ERR_FORMAT)
+    if (!p || i >= p->n || !out || i >= p->wins.size() || p->wins[i].w == 0 || p->wins[i].h == 0) return JPGPU_ERR_FORMAT;
+    *out = p->wins[i];
     return JPGPU_OK;
 }
 size_t jpgpu_pipeline_pixel_bytes(const jpgpu_pipeline *p, uint32_t i) {
@@ -1571,7 +1631,7 @@ int jpgpu_pipeline_last_timings(const jpgpu_pipeline *p, jpgpu_pipeline_timings 
 // copy of one sub-batch runs while the next ones decode; nothing to reduce — SURVEY 8e); jpgpu_pipeline_pixels_device then points
 // into the copies.  gather_ms = what the call still waited for the copies after the last child had decoded (the exposed part),
 // gather_copy_ms = the longest child's summed copy time (events around each copy).
-static int multi_decode(jpgpu_pipeline *p, const uint8_t *const *data, const size_t *len, uint32_t n, uint32_t flags) {
+static int multi_decode(jpgpu_pipeline *p, const uint8_t *const *data, const size_t *len, const jpgpu_window *windows, uint32_t n, uint32_t flags) {
     const double t0 = now_ms(), cpu0 = process_cpu_ms();
     const uint32_t nc = (uint32_t)p->children.size();
     const bool gather = (flags & JPGPU_PIPELINE_GATHER) != 0;
@@ -1583,9 +1643,11 @@ static int multi_decode(jpgpu_pipeline *p, const uint8_t *const *data, const siz
             if (!p->peer_error[k].empty()) return jpgpu::set_err(p->err, JPGPU_ERR_IO, "gather: %s", p->peer_error[k].c_str());
     std::vector<std::vector<const uint8_t *>> cd(nc);
     std::vector<std::vector<size_t>> cl(nc);
+    std::vector<std::vector<jpgpu_window>> cw(nc);
     for (uint32_t i = 0; i < n; i++) {
         cd[i % nc].push_back(data[i]);
         cl[i % nc].push_back(len[i]);
+        if (windows) cw[i % nc].push_back(windows[i]);
     }
     std::vector<int> rcs(nc, JPGPU_OK);
     std::vector<std::thread> th;
@@ -1594,7 +1656,7 @@ static int multi_decode(jpgpu_pipeline *p, const uint8_t *const *data, const siz
         p->children[k]->gather_device = p->device;
         th.emplace_back([&, k] {
             pin_to(p->child_cpus[k]);  // (the call's uploader thread starts from here and inherits the mask)
-            rcs[k] = jpgpu_pipeline_decode(p->children[k], cd[k].data(), cl[k].data(), (uint32_t)cd[k].size(), child_flags);
+            rcs[k] = jpgpu_pipeline_decode_windowed(p->children[k], cd[k].data(), cl[k].data(), windows ? cw[k].data() : nullptr, (uint32_t)cd[k].size(), child_flags);
         });
     }
     for (auto &t : th) t.join();
@@ -1626,6 +1688,7 @@ static int multi_decode(jpgpu_pipeline *p, const uint8_t *const *data, const siz
         p->t.images_device_progressive += c->t.images_device_progressive;
         p->t.images_host_light += c->t.images_host_light;
         p->t.images_entry_pixels += c->t.images_entry_pixels;
+        p->t.images_windowed += c->t.images_windowed;
         p->t.input_pinned |= c->t.input_pinned;
     }
     p->t.decode_ms = t1 - t0;

@@ -172,6 +172,25 @@ __host__ __device__ inline void window_tile_blocks(const WindowGeom &g, uint32_t
     bx1 = bx1 > (int32_t)g.block_w[c] ? (int32_t)g.block_w[c] : bx1, by1 = by1 > (int32_t)g.block_h[c] ? (int32_t)g.block_h[c] : by1;
 }
 
+// The rows of blocks of component c that the launch's tiles can touch (the union of window_tile_blocks' rows over every tile and
+// band): [r0, r1) — and the same as whole MCU rows of the frame over all components, [my0, my1): what the device entropy route has
+// to leave in the coefficient arena for a windowed image (HuffSyncJob::keep_my0 / keep_my1).  No HIP dependency (tests/emu).
+inline void window_kept_rows(const WindowGeom &g, uint32_t c, uint32_t &r0, uint32_t &r1) {
+    const uint32_t lo = g.oy * g.v[c], hi = g.ey * g.v[c] + g.halo[c];
+    r0 = lo > g.halo[c] ? lo - g.halo[c] : 0u;
+    r1 = hi < g.block_h[c] ? hi : g.block_h[c];
+}
+inline void window_kept_mcu_rows(const WindowGeom &g, uint32_t &my0, uint32_t &my1) {
+    my0 = g.mcu_h, my1 = 0u;
+    for (uint32_t c = 0; c < g.ncomp; c++) {
+        uint32_t r0, r1;
+        window_kept_rows(g, c, r0, r1);
+        const uint32_t a = r0 / g.v[c], b = (r1 + g.v[c] - 1u) / g.v[c];
+        my0 = a < my0 ? a : my0, my1 = b > my1 ? b : my1;
+    }
+    my1 = my1 < g.mcu_h ? my1 : g.mcu_h;
+}
+
 // A run of 4 * ND bytes (d[k] holds bytes 4k .. 4k + 3, little-endian) to `o` whatever its alignment — window rows of w * 3 or
 // w bytes start anywhere: aligned dword stores, and the bytes before the first / after the last 4-byte boundary one by one
 // (ND - 1 dword + 4 byte stores where the unit's bytes one by one were 4 * ND stores).

@@ -61,6 +61,15 @@ class Decoder:
         self._check(N.lib().jpgpu_decoder_scale(self._h, requested_width, requested_height, C.byref(w), C.byref(h)))
         return w.value, h.value
 
+    def set_window(self, x, y, w, h):
+        """decode() then returns only the window (x, y, w, h) of the output grid (after ``scale``): that slice of the whole decode,
+        packed, as ``Batch(windows=)`` defines it.  w == 0 or h == 0: the whole image again.  A window outside the output fails
+        decode() with a FormatError."""
+        x, y, w, h = (int(v) for v in (x, y, w, h))
+        if min(x, y, w, h) < 0 or max(x, y, w, h) > 65535:
+            raise ValueError(f"window {(x, y, w, h)!r}")
+        self._check(N.lib().jpgpu_decoder_set_window(self._h, x, y, w, h))
+
     def decode(self):
         """decode() -> Vec<u8> (a numpy uint8 array)."""
         n = C.c_size_t(0)

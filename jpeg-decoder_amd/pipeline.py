@@ -9,6 +9,7 @@ import ctypes as C
 import numpy as np
 
 from . import _native as N
+from .batch import window_structs
 from .decoder import CODING_PROCESSES, PIXEL_FORMATS, ImageInfo
 from .error import check, error_for_status
 from .worker import color_transform_id
@@ -74,7 +75,7 @@ class Pipeline:
     __del__ = close
 
     def decode(self, streams, download=True, dense=False, device_entropy=True, scale=None, color_transform=None, max_decoding_buffer_size=None,
-               gather=False, host_light=None, input_pinned=False, progressive_on_host=False):
+               gather=False, host_light=None, input_pinned=False, progressive_on_host=False, windows=None):
         """-> list with, per stream, a numpy uint8 array of the decoded pixels (``Decoder.decode()``'s Vec<u8>) or the
         ``Error`` instance that stream produced.  download=False leaves the pixels in HBM (see ``device_pointer``); dense=True sends all
         64 coefficients of every block over PCIe instead of the compact form (same pixels, A/B switch); device_entropy=True
@@ -87,27 +88,39 @@ class Pipeline:
         download="pinned": copy the pixels to the pipeline's pinned host buffers but return byte counts — look at them with ``pixels_host(i)``
         (no Python copy per image); host_light=True / False: JPGPU_PIPELINE_HOST_LIGHT / _HOST_STAGED (None: the library's default — host light,
         at every thread count); streams may be a ``PinnedFiles`` arena, with input_pinned=True the device reads it directly;
-        progressive_on_host=True: progressive frames on the host entropy decoder even with device_entropy (A/B)."""
-        L = N.lib()
-        check(L.jpgpu_pipeline_set_max_decoding_buffer_size(self._h, (1 << 64) - 1 if max_decoding_buffer_size is None else int(max_decoding_buffer_size)), b"set_max")
-        check(L.jpgpu_pipeline_set_color_transform(self._h, color_transform_id(color_transform) if color_transform is not None else -1), b"set_color_transform")
-        check(L.jpgpu_pipeline_set_scale(self._h, *((int(scale[0]), int(scale[1])) if scale else (0, 0))), b"set_scale")
+        progressive_on_host=True: progressive frames on the host entropy decoder even with device_entropy (A/B);
+        windows: None, one (x, y, w, h) for every stream, or a list with a tuple or None per stream (the convention of ``Batch(windows=)``):
+        the stream's pixels are then that slice of its whole decode, packed — ``full.reshape(H, W, nc)[y:y+h, x:x+w]``
+        (``full.reshape(H, nc, W)[y:y+h, :, x:x+w]`` for color_transform "None" with more than one component) — in the pixel grid of the
+        image's output, i.e. after `scale`.  A window outside its image fails that stream alone (FormatError in the result list);
+        ``window(i)`` gives the window decoded, ``info(i)`` keeps the image's size.  The arrays stay flat uint8."""
         if isinstance(streams, PinnedFiles):
+            bufs = None
             n = len(streams)
-            ptrs = (C.c_void_p * max(n, 1))(*[streams.base + o for o in streams.offsets])
-            lens = (C.c_size_t * max(n, 1))(*streams.lengths)
         else:
             if input_pinned:
                 raise ValueError("input_pinned=True needs a PinnedFiles arena")
             bufs = [bytes(s.read() if hasattr(s, "read") else s) for s in streams]
             n = len(bufs)
+        wins = window_structs(windows, n)  # (raises on a list of the wrong length, before anything native is called)
+        L = N.lib()
+        check(L.jpgpu_pipeline_set_max_decoding_buffer_size(self._h, (1 << 64) - 1 if max_decoding_buffer_size is None else int(max_decoding_buffer_size)), b"set_max")
+        check(L.jpgpu_pipeline_set_color_transform(self._h, color_transform_id(color_transform) if color_transform is not None else -1), b"set_color_transform")
+        check(L.jpgpu_pipeline_set_scale(self._h, *((int(scale[0]), int(scale[1])) if scale else (0, 0))), b"set_scale")
+        if bufs is None:
+            ptrs = (C.c_void_p * max(n, 1))(*[streams.base + o for o in streams.offsets])
+            lens = (C.c_size_t * max(n, 1))(*streams.lengths)
+        else:
             ptrs = (C.c_char_p * max(n, 1))(*bufs)  # the bytes objects' own buffers (alive in `bufs` during the call): no copies
             lens = (C.c_size_t * max(n, 1))(*[len(b) for b in bufs])
         keep_pinned = download == "pinned"
         flags = ((N.PIPELINE_DOWNLOAD if download else 0) | (N.PIPELINE_DENSE if dense else 0) | (N.PIPELINE_DEVICE_ENTROPY if device_entropy else 0) |
                  (N.PIPELINE_GATHER if gather else 0) | (N.PIPELINE_INPUT_PINNED if input_pinned else 0) | (N.PIPELINE_PROGRESSIVE_ON_HOST if progressive_on_host else 0) |
                  (0 if host_light is None else (N.PIPELINE_HOST_LIGHT if host_light else N.PIPELINE_HOST_STAGED)))
-        st = L.jpgpu_pipeline_decode(self._h, C.cast(ptrs, C.POINTER(C.c_void_p)), lens, n, flags)
+        if wins is None:
+            st = L.jpgpu_pipeline_decode(self._h, C.cast(ptrs, C.POINTER(C.c_void_p)), lens, n, flags)
+        else:
+            st = L.jpgpu_pipeline_decode_windowed(self._h, C.cast(ptrs, C.POINTER(C.c_void_p)), lens, wins, n, flags)
         check(st, L.jpgpu_pipeline_last_error(self._h) if st else b"")
         out = []
         for i in range(n):
@@ -129,6 +142,14 @@ class Pipeline:
         if N.lib().jpgpu_pipeline_image_info(self._h, image, C.byref(i)):
             return None
         return ImageInfo(i.width, i.height, PIXEL_FORMATS[i.pixel_format], CODING_PROCESSES[i.coding_process])
+
+    def window(self, image):
+        """jpgpu_pipeline_image_window: (x, y, w, h) the image of the last call was decoded with — (0, 0, W, H) of its output grid
+        when it had no window; None for an image without a frame or whose window was refused."""
+        w = N.Window()
+        if N.lib().jpgpu_pipeline_image_window(self._h, image, C.byref(w)):
+            return None
+        return w.x, w.y, w.w, w.h
 
     def download(self, image):
         """jpgpu_pipeline_download: one image's pixels of the last call from HBM (for calls made with download=False)."""
