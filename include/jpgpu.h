@@ -161,6 +161,34 @@ typedef struct jpgpu_window {
  * refuses (components at different dct_scales) with JPGPU_ERR_UNSUPPORTED and the reason in jpgpu_batch_last_error. */
 int jpgpu_batch_create_windowed(int device, const jpgpu_image_desc *descs, const jpgpu_window *windows, uint32_t n_images,
                                 uint32_t flags, jpgpu_batch **out);
+/* ---- A fixed output size: every image resampled to out_w x out_h on the device -----------------------------------------------
+ * jpgpu_batch_create_windowed (`windows` may be NULL) with an output size, out_w and out_h in 1..2048.  The pixels of image i are
+ * the resample to out_w x out_h of what image i gives without it: its window, or its whole output when it has none (the grid after
+ * Decoder::scale; the colour transform is unchanged).  Every image's result is out_h * out_w * ncomp bytes, interleaved and packed.
+ * jpgpu_batch_out_bytes / out_offset, the output arena (the caller's with EXTERNAL_BUFFERS), jpgpu_batch_out_arena_bytes and
+ * jpgpu_batch_download hold the RESIZED pixels; the pixels the batch's other kernels write go, by the same routes and launches, to an
+ * intermediate arena the batch always owns, and one more launch behind them on the same stream resamples every image
+ * (jpgpu_batch_path gains the suffix "+resize").  An out_w or out_h of 0 or above 2048 fails creation with JPGPU_ERR_FORMAT; planar
+ * output (ColorTransform None with more than one component) with JPGPU_ERR_UNSUPPORTED.
+ *
+ * The arithmetic is the 8-bit integer bilinear resample with antialiasing that Pillow's Image.resize(size, BILINEAR) performs on the
+ * cropped image — crop, then resize: nothing outside the window is read.  PRECISION_BITS = 22.  Per axis, from in_size to out_size,
+ * in IEEE double:
+ *   1. scale = in_size / out_size, fs = max(scale, 1.0), support = fs, ksize = ceil(support) * 2 + 1, ss = 1.0 / fs.
+ *   2. for output index xx: center = (xx + 0.5) * scale, xmin = max((int)(center - support + 0.5), 0),
+ *      xmax = min((int)(center + support + 0.5), in_size), n = xmax - xmin.
+ *   3. for x < n: a = |(x + xmin - center + 0.5) * ss|, w[x] = a < 1 ? 1 - a : 0; ww = the sum of w[x] in index order.
+ *   4. k[x] = (int)(w[x] / ww * 2^22 + 0.5)   (never negative).
+ *   5. one pass: out = clamp((2^21 + sum p[xmin + x] * k[x]) >> 22, 0, 255) in 32-bit integers (the sum stays below 2^31).
+ *   6. the horizontal pass runs first and is rounded to u8; the vertical pass runs on its result.
+ * An axis whose size does not change yields the identity (k = {2^22, 0}).  One known difference from Pillow: its Python wrapper runs
+ * the vertical pass first when H > 100 W and out_h < H (+-1 on such images); this library never does. */
+int jpgpu_batch_create_resized(int device, const jpgpu_image_desc *descs, const jpgpu_window *windows, uint16_t out_w, uint16_t out_h,
+                               uint32_t n_images, uint32_t flags, jpgpu_batch **out);
+/* The tables of one axis as the batch computes them (pure host function, no device needed): `bounds` receives out_size pairs
+ * (xmin, n), `coefs` out_size x ksize int32 weights, zero beyond n; *ksize the row length.  With `bounds` and `coefs` NULL only
+ * *ksize is set (to size the buffers).  in_size and out_size are 1..65535; anything else is JPGPU_ERR_FORMAT. */
+int jpgpu_resample_coefficients(uint32_t in_size, uint32_t out_size, int32_t *bounds, int32_t *coefs, uint32_t *ksize);
 void jpgpu_batch_destroy(jpgpu_batch *b);
 const char *jpgpu_batch_last_error(const jpgpu_batch *b);
 

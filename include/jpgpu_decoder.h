@@ -113,7 +113,9 @@ typedef struct jpgpu_pipeline_timings {
      *                 + DC sums of scans whose components share their tables; images_entry_pixels (below): only the strip index of
      *                 their lists — the pixel walk reads the lists itself
      *   dev_pixel_ms  class finalize + pixel kernels (dequantize, IDCT, upsampling, colour conversion) */
-    uint32_t dev_times_valid, _pad;
+    uint32_t dev_times_valid;
+    uint32_t images_resized; /* (in what was padding, with jpgpu_pipeline_set_output_size) decoded images resampled to the output size:
+                              * all of them while one is set, else 0 */
     double dev_fill_ms, dev_sync_ms, dev_write_ms, dev_pixel_ms;
     /* pipelines over several devices (jpgpu_pipeline_create_multi): wall clock until every device had decoded its share, then of the
      * gather to the first device (JPGPU_PIPELINE_GATHER; 0 without) and the bytes it moved.  The other wall-clock fields are then the
@@ -216,6 +218,17 @@ const char *jpgpu_pipeline_last_error(const jpgpu_pipeline *p);
  * per image, as N decoders on which scale() was called would; jpgpu_pipeline_image_info then reports the scaled size.
  * 0 x 0: full size again (the default). */
 int jpgpu_pipeline_set_scale(jpgpu_pipeline *p, uint16_t requested_width, uint16_t requested_height);
+/* A fixed output size for every image of the calls that follow (sticky, like the scale): each image's pixels are the resample to
+ * width x height (1..2048 each; the arithmetic of jpgpu_batch_create_resized, jpgpu.h) of what it would give without — its window
+ * (jpgpu_pipeline_decode_windowed), or its whole output, in the grid after jpgpu_pipeline_set_scale — so every decoded image is
+ * height * width * ncomp bytes, interleaved.  jpgpu_pipeline_pixel_bytes / _pixels_device / _pixels_host / _download, the pinned
+ * download block, the JPGPU_PIPELINE_GATHER copies and timings.pixel_bytes hold / count the RESIZED bytes (only those cross the link);
+ * jpgpu_pipeline_image_info and _image_window keep reporting the image and its window; timings.images_resized counts the images.
+ * An image with planar output (ColorTransform None, more than one component) fails alone with JPGPU_ERR_UNSUPPORTED.  0 x 0 switches
+ * it off (the default: same routes, kernels, launches and bytes as ever); any other size with a 0 or above 2048 is JPGPU_ERR_FORMAT and
+ * changes nothing.  A change of the output size between calls creates the kept sub-batches anew; fresh windows at the same output
+ * size are set in place. */
+int jpgpu_pipeline_set_output_size(jpgpu_pipeline *p, uint16_t width, uint16_t height);
 /* Decoder::set_color_transform (src/decoder.rs:158-161) for every image of the calls that follow: one of the JPGPU_CT_* values of
  * jpgpu.h instead of what determine_color_transform finds per image; a negative value: per image again (the default). */
 int jpgpu_pipeline_set_color_transform(jpgpu_pipeline *p, int color_transform);

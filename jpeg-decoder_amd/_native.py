@@ -74,7 +74,7 @@ class PipelineTimings(C.Structure):
     _fields_ = [(n, C.c_double) for n in ("headers_ms", "setup_ms", "entropy_and_upload_ms", "kernels_ms", "download_ms", "total_ms")] + \
                [("threads", C.c_uint32), ("images_ok", C.c_uint32), ("jpeg_bytes", C.c_uint64), ("coefficient_bytes", C.c_uint64),
                 ("pixel_bytes", C.c_uint64), ("images_device_entropy", C.c_uint32), ("images_device_rejected", C.c_uint32),
-                ("dev_times_valid", C.c_uint32), ("_pad", C.c_uint32)] + \
+                ("dev_times_valid", C.c_uint32), ("images_resized", C.c_uint32)] + \
                [(n, C.c_double) for n in ("dev_fill_ms", "dev_sync_ms", "dev_write_ms", "dev_pixel_ms", "decode_ms", "gather_ms")] + \
                [("gather_bytes", C.c_uint64), ("gather_copy_ms", C.c_double), ("cpu_ms", C.c_double), ("images_host_light", C.c_uint32),
                 ("input_pinned", C.c_uint32), ("images_device_progressive", C.c_uint32), ("images_entry_pixels", C.c_uint32), ("images_windowed", C.c_uint32)]
@@ -123,6 +123,9 @@ _PROTOS = {
                                       C.c_uint16, C.c_int, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]),
     "jpgpu_batch_create": (C.c_int, [C.c_int, C.POINTER(ImageDesc), C.c_uint32, C.c_uint32, C.POINTER(C.c_void_p)]),
     "jpgpu_batch_create_windowed": (C.c_int, [C.c_int, C.POINTER(ImageDesc), C.POINTER(Window), C.c_uint32, C.c_uint32, C.POINTER(C.c_void_p)]),
+    "jpgpu_batch_create_resized": (C.c_int, [C.c_int, C.POINTER(ImageDesc), C.POINTER(Window), C.c_uint16, C.c_uint16, C.c_uint32, C.c_uint32,
+                                             C.POINTER(C.c_void_p)]),
+    "jpgpu_resample_coefficients": (C.c_int, [C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.POINTER(C.c_uint32)]),
     "jpgpu_batch_destroy": (None, [C.c_void_p]),
     "jpgpu_batch_last_error": (C.c_char_p, [C.c_void_p]),
     "jpgpu_batch_coef_arena_bytes": (C.c_size_t, [C.c_void_p]),
@@ -189,6 +192,7 @@ _PROTOS = {
     "jpgpu_pipeline_pixels_host": (C.c_void_p, [C.c_void_p, C.c_uint32]),
     "jpgpu_pipeline_kernel_path": (C.c_char_p, [C.c_void_p]),
     "jpgpu_pipeline_set_scale": (C.c_int, [C.c_void_p, C.c_uint16, C.c_uint16]),
+    "jpgpu_pipeline_set_output_size": (C.c_int, [C.c_void_p, C.c_uint16, C.c_uint16]),
     "jpgpu_pipeline_set_color_transform": (C.c_int, [C.c_void_p, C.c_int]),
     "jpgpu_pipeline_set_max_decoding_buffer_size": (C.c_int, [C.c_void_p, C.c_size_t]),
     "jpgpu_pipeline_download": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]),

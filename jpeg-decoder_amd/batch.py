@@ -39,6 +39,14 @@ def window_structs(windows, n):
     return arr
 
 
+def output_size_pair(output_size):
+    """(w, h) of an output size as two ints that fit the C ABI's uint16 (the library checks the range 1..2048 itself)."""
+    w, h = (int(v) for v in output_size)
+    if min(w, h) < 0 or max(w, h) > 65535:
+        raise ValueError(f"output size {output_size!r}")
+    return w, h
+
+
 class Batch:
     """N independent images decoded per launch (jpgpu_batch_*).
 
@@ -48,13 +56,22 @@ class Batch:
     ``full.reshape(H, W, nc)[y:y+h, x:x+w]`` for interleaving colour functions, ``full.reshape(H, nc, W)[y:y+h, :, x:x+w]`` for
     ColorTransform None with more than one component.  out_bytes / download / the output arena hold the window's bytes.  A
     window that covers the whole image (or None, or w == 0 or h == 0) is no window; one outside its image fails creation
-    (FormatError)."""
+    (FormatError).
 
-    def __init__(self, descs, device=0, flags=N.BATCH_DEFAULT, windows=None):
+    output_size: None or (w, h), each 1..2048 (jpgpu_batch_create_resized).  Every image's pixels are then the 8-bit bilinear resample
+    with antialiasing (Pillow's ``Image.resize((w, h), BILINEAR)`` arithmetic, crop first, horizontal pass first)
+    of what it gives without: its window, or its whole output.  out_bytes / out_offset / download / the output arena hold h * w * nc
+    bytes per image, interleaved; `path` ends in "+resize".  Planar output (ColorTransform None, more than one component) is refused
+    (UnsupportedError), a size of 0 or above 2048 is a FormatError."""
+
+    def __init__(self, descs, device=0, flags=N.BATCH_DEFAULT, windows=None, output_size=None):
         self._h = C.c_void_p()
         arr = (N.ImageDesc * len(descs))(*descs)
         wins = window_structs(windows, len(descs))
-        if wins is None:
+        self.output_size = None if output_size is None else output_size_pair(output_size)
+        if self.output_size is not None:
+            st = N.lib().jpgpu_batch_create_resized(device, arr, wins, self.output_size[0], self.output_size[1], len(descs), flags, C.byref(self._h))
+        elif wins is None:
             st = N.lib().jpgpu_batch_create(device, arr, len(descs), flags, C.byref(self._h))
         else:
             st = N.lib().jpgpu_batch_create_windowed(device, arr, wins, len(descs), flags, C.byref(self._h))

@@ -16,6 +16,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <deque>
+#include <map>
 #include <string>
 #include <vector>
 
@@ -30,6 +31,7 @@
 #include "host_common.hpp"
 #include "kernels.hpp"
 #include "range_stats.hpp"
+#include "resample_band.hpp"
 #include "window_band.hpp"
 
 using namespace jpgpu;
@@ -87,6 +89,19 @@ struct jpgpu_batch {
     ImageJob *d_w_image_jobs = nullptr;
     uint32_t w_max_tiles_x = 0, w_max_bands = 0, w_lds_bytes = 0;
     bool w_scales[9] = {false, false, false, false, false, false, false, false, false};
+    // A fixed output size (jpgpu_batch_create_resized, resample_band.hpp; rs_w == 0: none).  The output arena (d_out, out_off, out_len,
+    // out_bytes) then holds rs_h x rs_w x ncomp bytes per image, and every pixel kernel above writes what it always writes — the window's
+    // or the whole image's pixels — into an intermediate arena the batch owns (d_pix, pix_off, pix_len), which one more launch resamples.
+    uint32_t rs_w = 0, rs_h = 0;
+    std::vector<size_t> pix_off, pix_len;
+    size_t pix_bytes = 0, pix_cap = 0;
+    uint8_t *d_pix = nullptr;
+    std::vector<ResampleJob> rs_jobs;  // per image
+    std::vector<int32_t> rs_tab;       // the images' tables (equal axes share one)
+    ResampleJob *d_rs_jobs = nullptr;
+    int32_t *d_rs_tab = nullptr;
+    size_t rs_tab_cap = 0;             // int32 words behind d_rs_tab
+    uint32_t rs_max_bands = 0, rs_lds_bytes = 0;
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
     // compact transport (compact.hpp): staging area in HBM, allocated at the first jpgpu_batch_upload_compact
     std::mutex compact_mutex;
@@ -146,6 +161,61 @@ struct jpgpu_batch {
         if (_e != hipSuccess) return set_err(b->err, JPGPU_ERR_IO, "%s: %s", #call, hipGetErrorString(_e)); \
     } while (0)
 
+// where the pixel kernels write: the output arena, or the intermediate one of a batch with an output size
+static uint8_t *pix_base(const jpgpu_batch *b) { return b->rs_w ? b->d_pix : b->d_out; }
+static const std::vector<size_t> &pix_offsets(const jpgpu_batch *b) { return b->rs_w ? b->pix_off : b->out_off; }
+
+// The resample tables and bands of every image from its source size (its window's, else its output grid's): at creation and after
+// batch_rewindow.  Axes of equal (in, out) sizes share one table.
+static int batch_resample_tables(jpgpu_batch *b) {
+    const uint32_t n = (uint32_t)b->descs.size();
+    b->rs_jobs.assign(n, ResampleJob{});
+    b->rs_tab.clear();
+    b->rs_max_bands = b->rs_lds_bytes = 0;
+    std::map<uint64_t, std::pair<uint32_t, uint32_t>> seen;  // (in, out) -> offsets of bounds, coefficients
+    auto axis = [&](uint32_t in, uint32_t out, uint32_t &bo, uint32_t &ko, uint32_t &ks) {
+        ks = resample_ksize(in, out);
+        const uint64_t key = ((uint64_t)in << 32) | out;
+        auto it = seen.find(key);
+        if (it != seen.end()) return bo = it->second.first, ko = it->second.second, true;
+        const size_t base = b->rs_tab.size(), end = base + 2u * (size_t)out + (size_t)out * ks;
+        if (end > 0xffffffffull) return false;
+        b->rs_tab.resize(end);
+        bo = (uint32_t)base, ko = (uint32_t)(base + 2u * out);
+        resample_coefficients(in, out, b->rs_tab.data() + bo, b->rs_tab.data() + ko, ks);
+        seen[key] = {bo, ko};
+        return true;
+    };
+    size_t k = 0;
+    for (uint32_t i = 0; i < n; i++) {
+        const jpgpu_image_desc &d = b->descs[i];
+        ResampleJob &j = b->rs_jobs[i];
+        window_grid(d.components, d.ncomp, d.out_w, d.out_h, j.in_w, j.in_h);
+        if (k < b->win_ids.size() && b->win_ids[k] == i) j.in_w = b->win_geoms[k].ww, j.in_h = b->win_geoms[k].wh, k++;
+        j.nc = d.ncomp, j.out_w = b->rs_w, j.out_h = b->rs_h;
+        if (!axis(j.in_w, j.out_w, j.hb, j.hk, j.hks) || !axis(j.in_h, j.out_h, j.vb, j.vk, j.vks))
+            return set_err(b->err, JPGPU_ERR_UNSUPPORTED, "image %u: resample tables of the batch exceed 2^32 words", i);
+    }
+    for (uint32_t i = 0; i < n; i++) {  // (the tables stand still now)
+        ResampleJob &j = b->rs_jobs[i];
+        if (!resample_plan(j, b->rs_tab.data())) return set_err(b->err, JPGPU_ERR_INTERNAL, "image %u: no resample plan", i);
+        b->rs_max_bands = std::max(b->rs_max_bands, j.bands);
+        b->rs_lds_bytes = std::max(b->rs_lds_bytes, j.lds_bytes);
+    }
+    if (b->rs_tab.size() > b->rs_tab_cap) {
+        B_HIP(hipDeviceSynchronize());
+        if (b->d_rs_tab) (void)hipFree(b->d_rs_tab);
+        b->d_rs_tab = nullptr;
+        b->rs_tab_cap = 0;
+        const size_t cap = b->rs_tab.size() + b->rs_tab.size() / 4;
+        B_HIP(hipMalloc((void **)&b->d_rs_tab, cap * sizeof(int32_t)));
+        b->rs_tab_cap = cap;
+    }
+    B_HIP(hipMemcpy(b->d_rs_tab, b->rs_tab.data(), b->rs_tab.size() * sizeof(int32_t), hipMemcpyHostToDevice));
+    b->jobs_dirty = true;  // (the jobs go up with the others)
+    return JPGPU_OK;
+}
+
 // first use of the device-side classes: statistics (zeroed), class table, pinned staging
 static int batch_enable_dev_classes(jpgpu_batch *b) {
     if (b->d_stats) return JPGPU_OK;
@@ -196,6 +266,8 @@ static int batch_refresh_jobs(jpgpu_batch *b, hipStream_t stream = nullptr) {
     const bool need_bind = b->jobs_dirty || (b->cls_dirty && !b->dev_classes);
     if (!need_bind && !b->cls_dirty) return JPGPU_OK;
     if (!b->d_coef || !b->d_out) return set_err(b->err, JPGPU_ERR_FORMAT, "batch has no device buffers bound");
+    uint8_t *const pix = pix_base(b);
+    const std::vector<size_t> &pix_off = pix_offsets(b);
     if (b->dev_classes) {
         const size_t n4 = b->descs.size() * 4;
         const uint32_t k = b->cls_next++ % jpgpu_batch::kClsRing;
@@ -229,7 +301,7 @@ static int batch_refresh_jobs(jpgpu_batch *b, hipStream_t stream = nullptr) {
         ImageJob ij;
         size_t out_len = 0;
         int rc = build_image_job(d.components, d.ncomp, planes, d.out_w, d.out_h, d.color_transform,
-                                 b->d_out + b->out_off[i], ij, out_len, b->err);
+                                 pix + pix_off[i], ij, out_len, b->err);
         if (rc) return rc;
         b->image_jobs.push_back(ij);
     }
@@ -259,7 +331,7 @@ static int batch_refresh_jobs(jpgpu_batch *b, hipStream_t stream = nullptr) {
         }
         ImageJob ij;
         size_t out_len = 0;
-        int rc = build_image_job(d.components, d.ncomp, no_planes, d.out_w, d.out_h, d.color_transform, b->d_out + b->out_off[i], ij, out_len, b->err);
+        int rc = build_image_job(d.components, d.ncomp, no_planes, d.out_w, d.out_h, d.color_transform, pix + pix_off[i], ij, out_len, b->err);
         if (rc) return rc;
         b->s_image_jobs.push_back(ij);
     }
@@ -283,7 +355,7 @@ static int batch_refresh_jobs(jpgpu_batch *b, hipStream_t stream = nullptr) {
         }
         ImageJob ij;
         size_t out_len = 0;
-        int rc = build_image_job(d.components, d.ncomp, no_planes, d.out_w, d.out_h, d.color_transform, b->d_out + b->out_off[i], ij, out_len, b->err);
+        int rc = build_image_job(d.components, d.ncomp, no_planes, d.out_w, d.out_h, d.color_transform, pix + pix_off[i], ij, out_len, b->err);
         if (rc) return rc;
         b->w_image_jobs.push_back(ij);
     }
@@ -292,8 +364,12 @@ static int batch_refresh_jobs(jpgpu_batch *b, hipStream_t stream = nullptr) {
         B_HIP(hipMemcpy(b->d_w_image_jobs, b->w_image_jobs.data(), b->w_image_jobs.size() * sizeof(ImageJob), hipMemcpyHostToDevice));
     }
     for (FusedPlan &fp : b->fused) {
-        int rc = fused_bind(fp, b->d_coef, b->d_out, b->d_qt, b->coef_off, b->out_off, b->sane, b->err);
+        int rc = fused_bind(fp, b->d_coef, pix, b->d_qt, b->coef_off, pix_off, b->sane, b->err);
         if (rc) return rc;
+    }
+    if (b->rs_w) {
+        for (uint32_t i = 0; i < n; i++) b->rs_jobs[i].src = pix + pix_off[i], b->rs_jobs[i].dst = b->d_out + b->out_off[i];
+        B_HIP(hipMemcpy(b->d_rs_jobs, b->rs_jobs.data(), (size_t)n * sizeof(ResampleJob), hipMemcpyHostToDevice));
     }
     if (b->qt_dirty) {
         std::vector<uint16_t> qt((size_t)n * 4 * 64, 1);
@@ -309,8 +385,9 @@ static int batch_refresh_jobs(jpgpu_batch *b, hipStream_t stream = nullptr) {
 
 extern "C" {
 
-static int batch_create(int device, const jpgpu_image_desc *descs, const jpgpu_window *windows, uint32_t n_images, uint32_t flags,
-                        jpgpu_batch **out) {
+// rs_w, rs_h: the output size of jpgpu_batch_create_resized (0, 0: none)
+static int batch_create(int device, const jpgpu_image_desc *descs, const jpgpu_window *windows, uint32_t rs_w, uint32_t rs_h, uint32_t n_images,
+                        uint32_t flags, jpgpu_batch **out) {
     if (!out) return JPGPU_ERR_FORMAT;
     *out = nullptr;
     if (!descs || n_images == 0 || n_images > 65535) return JPGPU_ERR_FORMAT;
@@ -318,6 +395,9 @@ static int batch_create(int device, const jpgpu_image_desc *descs, const jpgpu_w
     *out = b;  // returned even on failure so the caller can read last_error, then destroy
     b->device = device;
     b->flags = flags;
+    const bool resized = rs_w != 0 || rs_h != 0;
+    if (resized && (rs_w == 0 || rs_h == 0 || rs_w > RS_MAX_OUT || rs_h > RS_MAX_OUT))
+        return set_err(b->err, JPGPU_ERR_FORMAT, "output size %ux%u: width and height must be 1..%u", rs_w, rs_h, RS_MAX_OUT);
     int rc = use_device(device, b->err);
     if (rc) return rc;
     b->descs.assign(descs, descs + n_images);
@@ -345,6 +425,8 @@ static int batch_create(int device, const jpgpu_image_desc *descs, const jpgpu_w
         rc = build_image_job(d.components, d.ncomp, dummy, d.out_w, d.out_h, d.color_transform, nullptr, ij, out_len, b->err);
         if (rc) return rc;
         b->out_full_len[i] = out_len;
+        if (resized && ij.color_fn == CC_NONE && d.ncomp > 1)
+            return set_err(b->err, JPGPU_ERR_UNSUPPORTED, "image %u: no output size for planar output (ColorTransform None with %u components)", i, d.ncomp);
         // a window smaller than the image: the window group (an empty window or one that covers the image is no window)
         bool windowed = false;
         if (windows && windows[i].w != 0 && windows[i].h != 0) {
@@ -410,6 +492,17 @@ static int batch_create(int device, const jpgpu_image_desc *descs, const jpgpu_w
     b->coef_bytes = std::max<size_t>(co, 256);
     b->out_bytes = std::max<size_t>(oo, 256);
     b->plane_bytes_total = std::max<size_t>(po, 256);
+    if (resized) {  // what was laid out so far is the intermediate arena; the output arena holds rs_h x rs_w x ncomp bytes per image
+        b->rs_w = rs_w, b->rs_h = rs_h;
+        b->pix_off = b->out_off, b->pix_len = b->out_len, b->pix_bytes = b->out_bytes;
+        oo = 0;
+        for (uint32_t i = 0; i < n_images; i++) {
+            b->out_off[i] = oo;
+            b->out_len[i] = (size_t)rs_w * rs_h * b->descs[i].ncomp;
+            oo += align_up(b->out_len[i], 256);
+        }
+        b->out_bytes = std::max<size_t>(oo, 256);
+    }
 
     {
         std::vector<uint32_t> keys;
@@ -435,6 +528,7 @@ static int batch_create(int device, const jpgpu_image_desc *descs, const jpgpu_w
     if (!b->scaled_ids.empty()) b->path = (b->fused.empty() && b->generic_ids.empty()) ? b->scaled_name : "mixed";
     if (!b->win_ids.empty()) b->path = b->path.empty() ? "window" : "mixed";
     if (b->path.empty()) b->path = "generic";
+    if (resized) b->path += "+resize";
     hipError_t e;
 #define C_HIP(call)                                                                        \
     if ((e = (call)) != hipSuccess) return set_err(b->err, JPGPU_ERR_IO, "%s: %s", #call, hipGetErrorString(e))
@@ -444,9 +538,16 @@ static int batch_create(int device, const jpgpu_image_desc *descs, const jpgpu_w
         // (with windows: a quarter more than these need, at most what the whole images take — batch_rewindow sets other windows in place)
         size_t full = 0;
         for (size_t v : b->out_full_len) full += align_up(v, 256);
-        b->out_cap = b->win_ids.empty() ? b->out_bytes : std::max(b->out_bytes, std::min(std::max<size_t>(full, 256), b->out_bytes + b->out_bytes / 4));
+        b->out_cap = (b->win_ids.empty() || resized) ? b->out_bytes : std::max(b->out_bytes, std::min(std::max<size_t>(full, 256), b->out_bytes + b->out_bytes / 4));
         C_HIP(hipMalloc((void **)&b->d_out, b->out_cap));
         b->own_out = true;
+    }
+    if (resized) {  // (the same headroom for other windows, in the intermediate arena)
+        size_t full = 0;
+        for (size_t v : b->out_full_len) full += align_up(v, 256);
+        b->pix_cap = b->win_ids.empty() ? b->pix_bytes : std::max(b->pix_bytes, std::min(std::max<size_t>(full, 256), b->pix_bytes + b->pix_bytes / 4));
+        C_HIP(hipMalloc((void **)&b->d_pix, b->pix_cap));
+        C_HIP(hipMalloc((void **)&b->d_rs_jobs, (size_t)n_images * sizeof(ResampleJob)));
     }
     if (!b->generic_ids.empty()) C_HIP(hipMalloc((void **)&b->d_planes, b->plane_bytes_total));
     for (FusedPlan &fp : b->fused) {
@@ -490,15 +591,26 @@ static int batch_create(int device, const jpgpu_image_desc *descs, const jpgpu_w
     C_HIP(hipEventCreate(&b->ev0));
     C_HIP(hipEventCreate(&b->ev1));
 #undef C_HIP
+    if (resized) return batch_resample_tables(b);
     return JPGPU_OK;
 }
 
 int jpgpu_batch_create(int device, const jpgpu_image_desc *descs, uint32_t n_images, uint32_t flags, jpgpu_batch **out) {
-    return batch_create(device, descs, nullptr, n_images, flags, out);
+    return batch_create(device, descs, nullptr, 0, 0, n_images, flags, out);
 }
 int jpgpu_batch_create_windowed(int device, const jpgpu_image_desc *descs, const jpgpu_window *windows, uint32_t n_images, uint32_t flags,
                                 jpgpu_batch **out) {
-    return batch_create(device, descs, windows, n_images, flags, out);
+    return batch_create(device, descs, windows, 0, 0, n_images, flags, out);
+}
+int jpgpu_batch_create_resized(int device, const jpgpu_image_desc *descs, const jpgpu_window *windows, uint16_t out_w, uint16_t out_h,
+                               uint32_t n_images, uint32_t flags, jpgpu_batch **out) {
+    if (out_w == 0 || out_h == 0) {  // (0, 0 would mean "none" below: refuse it here)
+        if (!out) return JPGPU_ERR_FORMAT;
+        jpgpu_batch *b = new jpgpu_batch();
+        *out = b;
+        return set_err(b->err, JPGPU_ERR_FORMAT, "output size %ux%u: width and height must be 1..%u", out_w, out_h, RS_MAX_OUT);
+    }
+    return batch_create(device, descs, windows, out_w, out_h, n_images, flags, out);
 }
 
 void jpgpu_batch_destroy(jpgpu_batch *b) {
@@ -509,6 +621,9 @@ void jpgpu_batch_destroy(jpgpu_batch *b) {
         if (b->own_coef && b->d_coef) hipFree(b->d_coef);
         if (b->own_out && b->d_out) hipFree(b->d_out);
         if (b->d_planes) hipFree(b->d_planes);
+        if (b->d_pix) hipFree(b->d_pix);
+        if (b->d_rs_jobs) hipFree(b->d_rs_jobs);
+        if (b->d_rs_tab) hipFree(b->d_rs_tab);
         if (b->d_qt) hipFree(b->d_qt);
         if (b->d_compact) hipFree(b->d_compact);
         if (b->d_expand_jobs) hipFree(b->d_expand_jobs);
@@ -1844,7 +1959,7 @@ int jpgpu::batch_check_window(const jpgpu_image_desc &d, const jpgpu_window &wn,
 // are the caller's): the caller creates a new batch then.  An image of the group whose new window covers its whole output stays in it.  The output arena grows when the new windows need more than it holds.
 int jpgpu::batch_rewindow(jpgpu_batch *b, const jpgpu_window *windows) {
     if (!b || !windows) return JPGPU_ERR_FORMAT;
-    if (!b->own_out || b->win_ids.empty()) return JPGPU_ERR_UNSUPPORTED;
+    if ((!b->own_out && !b->rs_w) || b->win_ids.empty()) return JPGPU_ERR_UNSUPPORTED;  // (with an output size the windows' bytes are the batch's own)
     const uint32_t n = (uint32_t)b->descs.size();
     std::vector<WindowGeom> geoms(b->win_ids.size());
     std::vector<jpgpu_window> eff(n, jpgpu_window{0, 0, 0, 0});  // members: the window they decode
@@ -1876,28 +1991,32 @@ int jpgpu::batch_rewindow(jpgpu_batch *b, const jpgpu_window *windows) {
     }
     int rc = use_device(b->device, b->err);
     if (rc) return rc;
+    // (with an output size the windows' bytes live in the intermediate arena: the resized arena never changes)
+    std::vector<size_t> &w_off = b->rs_w ? b->pix_off : b->out_off, &w_len = b->rs_w ? b->pix_len : b->out_len;
+    size_t &w_bytes = b->rs_w ? b->pix_bytes : b->out_bytes, &w_cap = b->rs_w ? b->pix_cap : b->out_cap;
+    uint8_t *&w_arena = b->rs_w ? b->d_pix : b->d_out;
     size_t oo = 0, full = 0;
     k = 0;
     for (uint32_t i = 0; i < n; i++) {
         const bool member = k < b->win_ids.size() && b->win_ids[k] == i;
         if (member) k++;
         const size_t len = member ? (size_t)eff[i].w * eff[i].h * b->descs[i].ncomp : b->out_full_len[i];
-        b->out_off[i] = oo;
-        b->out_len[i] = len;
+        w_off[i] = oo;
+        w_len[i] = len;
         oo += align_up(len, 256);
         full += align_up(b->out_full_len[i], 256);
     }
-    b->out_bytes = std::max<size_t>(oo, 256);
+    w_bytes = std::max<size_t>(oo, 256);
     b->jobs_dirty = true;  // (every job's output pointer, the fused plans' included)
-    if (b->out_bytes > b->out_cap) {
+    if (w_bytes > w_cap) {
         B_HIP(hipDeviceSynchronize());
-        if (b->d_out) (void)hipFree(b->d_out);
-        b->d_out = nullptr;
-        b->out_cap = 0;
+        if (w_arena) (void)hipFree(w_arena);
+        w_arena = nullptr;
+        w_cap = 0;
         // (a quarter more than asked for, at most what the whole images take: the totals of a loader's random crops differ little from call to call)
-        const size_t cap = std::max(b->out_bytes, std::min(std::max<size_t>(full, 256), b->out_bytes + b->out_bytes / 4));
-        B_HIP(hipMalloc((void **)&b->d_out, cap));
-        b->out_cap = cap;
+        const size_t cap = std::max(w_bytes, std::min(std::max<size_t>(full, 256), w_bytes + w_bytes / 4));
+        B_HIP(hipMalloc((void **)&w_arena, cap));
+        w_cap = cap;
     }
     b->win_geoms = geoms;
     b->w_max_tiles_x = b->w_max_bands = b->w_lds_bytes = 0;
@@ -1909,11 +2028,13 @@ int jpgpu::batch_rewindow(jpgpu_batch *b, const jpgpu_window *windows) {
         b->w_scales[wg.scale] = true;
     }
     B_HIP(hipMemcpy(b->d_win_geoms, b->win_geoms.data(), b->win_geoms.size() * sizeof(WindowGeom), hipMemcpyHostToDevice));
+    if (b->rs_w) return batch_resample_tables(b);
     return JPGPU_OK;
 }
 // bytes the output arena of the batch would hold without any window (what a pinned copy of it never needs more than)
 size_t jpgpu::batch_out_arena_bound(const jpgpu_batch *b) {
     size_t full = 0;
+    if (b && b->rs_w) return b->out_bytes;  // (an output size: the arena never changes)
     if (b)
         for (size_t v : b->out_full_len) full += align_up(v, 256);
     return std::max<size_t>(full, 256);
@@ -2023,6 +2144,8 @@ int jpgpu_batch_decode(jpgpu_batch *b, void *hip_stream) {
     if (!b->win_ids.empty())  // (windows: after the others)
         B_HIP(launch_window_band(b->d_win_geoms, b->d_w_image_jobs, b->d_w_plane_jobs, (uint32_t)b->win_ids.size(), b->w_max_tiles_x, b->w_max_bands,
                                  b->w_lds_bytes, b->w_scales, s));
+    if (b->rs_w)  // (an output size: every image's pixels, wherever the launches above left them in the intermediate arena)
+        B_HIP(launch_resample_band(b->d_rs_jobs, b->d_rs_tab, (uint32_t)b->descs.size(), b->rs_max_bands, b->rs_lds_bytes, s));
     if (b->phase_events_valid) B_HIP(hipEventRecord(b->ev_phase[5], s));
     return JPGPU_OK;
 }

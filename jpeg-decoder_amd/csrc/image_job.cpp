@@ -10,6 +10,7 @@
 #include "host_common.hpp"
 
 #include "compact.hpp"
+#include "resample_band.hpp"
 
 namespace jpgpu {
 
@@ -183,6 +184,14 @@ int jpgpu_range_class(const int16_t *coefficients, size_t len, const uint16_t q[
     }
     if (max_abs < (1 << 15)) return (max_col <= 5900) ? 3 : 1;
     return 0;
+}
+
+// the resample tables of one axis (resample_band.hpp; the batch fills its own with the same function)
+int jpgpu_resample_coefficients(uint32_t in_size, uint32_t out_size, int32_t *bounds, int32_t *coefs, uint32_t *ksize) {
+    if (in_size == 0 || out_size == 0 || in_size > 65535u || out_size > 65535u || !ksize || (!bounds) != (!coefs)) return JPGPU_ERR_FORMAT;
+    *ksize = jpgpu::resample_ksize(in_size, out_size);
+    if (bounds) jpgpu::resample_coefficients(in_size, out_size, bounds, coefs, *ksize);
+    return JPGPU_OK;
 }
 
 size_t jpgpu_compact_max_bytes(size_t n_blocks) { return jpgpu::compact_max_bytes(n_blocks); }

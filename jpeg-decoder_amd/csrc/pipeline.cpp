@@ -255,6 +255,7 @@ struct SubBatch {
     bool compact = false;             // layout of h_coef: compact regions (stage_off) or a mirror of the arena
     std::vector<size_t> stage_off;    // compact mode: [image*4 + comp] offset of the component's region in h_coef
     std::vector<jpgpu_window> wins;   // the window of every image as the batch was created with it (w == 0: none); empty: no image has one
+    uint16_t rs_w = 0, rs_h = 0;      // the output size the batch was created with (jpgpu_pipeline_set_output_size; 0 x 0: none)
     uint32_t remaining = 0;  // images not yet uploaded / failed (uploader thread only)
     hipEvent_t ready[kCopyStreams] = {nullptr, nullptr, nullptr, nullptr};
     hipEvent_t decoded = nullptr;  // recorded on the compute stream behind the sub-batch's pixel kernels: downloads and the gather wait for it
@@ -268,6 +269,7 @@ struct SubBatch {
         descs.clear();
         stage_off.clear();
         wins.clear();
+        rs_w = rs_h = 0;
     }
 };
 
@@ -307,6 +309,7 @@ struct jpgpu_pipeline {
     // download held back the kernels of the next sub-batch that shares the stream, and the copies of a call did not run back to back)
     hipStream_t d2h[kD2HStreams] = {};
     uint16_t req_w = 0, req_h = 0;  // jpgpu_pipeline_set_scale (0 x 0: full size)
+    uint16_t rs_w = 0, rs_h = 0;    // jpgpu_pipeline_set_output_size (0 x 0: none)
     int color_transform = -1;       // jpgpu_pipeline_set_color_transform (< 0: what every image says itself)
     size_t max_bytes = SIZE_MAX;    // jpgpu_pipeline_set_max_decoding_buffer_size
     uint32_t n_compute = kComputeStreamsDefault;  // streams in use (JPGPU_PIPE_STREAMS: tuning knob, up to kComputeStreams)
@@ -687,6 +690,7 @@ int jpgpu_pipeline_decode_windowed(jpgpu_pipeline *p, const uint8_t *const *data
                     probe.decode_to(nothing);  // throws what the image's decode() would throw
                 }
             }
+            bool planar = false;  // color_no_convert with more than one component: planar within a row
             {
                 // what compute_image would refuse for this frame (an impossible sampling combination, a colour function whose row
                 // copy would overrun: src/decoder.rs:1300-1336, src/upsampler.rs:20-45) fails THIS image here — a sub-batch is
@@ -708,6 +712,7 @@ int jpgpu_pipeline_decode_windowed(jpgpu_pipeline *p, const uint8_t *const *data
                     whole.decode_to(nothing);
                     throw DecodeError{v, why};
                 }
+                planar = probe.color_fn == jpgpu::CC_NONE && d.ncomp > 1;
             }
             cand[i] = d;
             {
@@ -718,6 +723,9 @@ int jpgpu_pipeline_decode_windowed(jpgpu_pipeline *p, const uint8_t *const *data
                 if (v != JPGPU_OK) throw DecodeError{v, why};
                 p->wins[i] = jpgpu_window{0, 0, (uint16_t)gw, (uint16_t)gh};
                 if (windowed) win[i] = p->wins[i] = windows[i];
+                // (an output size: planar output has no resample — the image fails alone, like a refused window)
+                if (p->rs_w && planar)
+                    throw DecodeError{JPGPU_ERR_UNSUPPORTED, "no output size for planar output (ColorTransform None with more than one component)"};
             }
             if (device_entropy && p->infos[i].coding_process == JPGPU_CODING_DCT_PROGRESSIVE) {
                 // a progressive frame: its scans as tracks for the device (huff_prog_wave.hpp), if the stream is plainly eligible;
@@ -831,7 +839,8 @@ int jpgpu_pipeline_decode_windowed(jpgpu_pipeline *p, const uint8_t *const *data
         // the batch itself; an image the device decoder hands back is decoded into memory of its own): for 4096 x 1080p that
         // would have been 28 GB of pinned host memory.
         const bool staged = j >= n_dev_subs;
-        bool reuse = sb.batch && descs.size() == sb.descs.size() && sb.compact == compact && (sb.h_coef != nullptr) == staged;
+        // (another output size: other tables, another output arena — the sub-batch is created anew)
+        bool reuse = sb.batch && descs.size() == sb.descs.size() && sb.compact == compact && (sb.h_coef != nullptr) == staged && sb.rs_w == p->rs_w && sb.rs_h == p->rs_h;
         for (size_t k = 0; reuse && k < descs.size(); k++) reuse = same_geometry(descs[k], sb.descs[k]);
         // ... and the same windows: the window group's geometry and the output offsets are made from them (a kept batch with other
         // windows would return the pixels of the old ones).  Other windows for the SAME set of windowed images — a loader's fresh
@@ -848,7 +857,8 @@ int jpgpu_pipeline_decode_windowed(jpgpu_pipeline *p, const uint8_t *const *data
         }
         if (!reuse) {
             sb.drop();
-            rc = jpgpu_batch_create_windowed(p->device, descs.data(), wins.empty() ? nullptr : wins.data(), (uint32_t)descs.size(), JPGPU_BATCH_DEFAULT, &sb.batch);
+            rc = p->rs_w ? jpgpu_batch_create_resized(p->device, descs.data(), wins.empty() ? nullptr : wins.data(), p->rs_w, p->rs_h, (uint32_t)descs.size(), JPGPU_BATCH_DEFAULT, &sb.batch)
+                         : jpgpu_batch_create_windowed(p->device, descs.data(), wins.empty() ? nullptr : wins.data(), (uint32_t)descs.size(), JPGPU_BATCH_DEFAULT, &sb.batch);
             if (rc) {
                 // a frame the pixel backend refuses (e.g. an impossible sampling combination) fails the images of
                 // its sub-batch the way the reference fails it in compute_image
@@ -864,6 +874,7 @@ int jpgpu_pipeline_decode_windowed(jpgpu_pipeline *p, const uint8_t *const *data
             }
             sb.descs = descs;
             sb.wins = wins;
+            sb.rs_w = p->rs_w, sb.rs_h = p->rs_h;
             sb.compact = compact;
             sb.h_coef_bytes = jpgpu_batch_coef_arena_bytes(sb.batch);
             if (compact) {  // worst-case compact size per component (12 B/block more than dense), 256-B aligned
@@ -1293,6 +1304,7 @@ int jpgpu_pipeline_decode_windowed(jpgpu_pipeline *p, const uint8_t *const *data
     p->t.images_host_light = light_images;
     p->t.images_entry_pixels = entry_images;
     p->t.images_windowed = windowed_images;
+    p->t.images_resized = p->rs_w ? okc : 0u;
     p->t.input_pinned = input_pinned ? 1u : 0u;
     if (trace && (prog_host_bytes || device_prog_images))
         fprintf(stderr, "pipeline trace: progressive frames: %u on the device (walk %.2f ms, launches + range scan + pixels %.2f ms), %u on the host (entropy phase %.2f ms, %.1f ns per byte and thread)\n",
@@ -1392,6 +1404,15 @@ int jpgpu_pipeline_set_scale(jpgpu_pipeline *p, uint16_t requested_width, uint16
     for (jpgpu_pipeline *c : p->children) jpgpu_pipeline_set_scale(c, requested_width, requested_height);
     p->req_w = requested_width;
     p->req_h = requested_height;
+    return JPGPU_OK;
+}
+int jpgpu_pipeline_set_output_size(jpgpu_pipeline *p, uint16_t width, uint16_t height) {
+    if (!p) return JPGPU_ERR_FORMAT;
+    if ((width != 0 || height != 0) && (width == 0 || height == 0 || width > 2048u || height > 2048u))
+        return jpgpu::set_err(p->err, JPGPU_ERR_FORMAT, "output size %ux%u: width and height must be 1..2048 (0 x 0: none)", width, height);
+    for (jpgpu_pipeline *c : p->children) jpgpu_pipeline_set_output_size(c, width, height);
+    p->rs_w = width;
+    p->rs_h = height;
     return JPGPU_OK;
 }
 uint32_t jpgpu_pipeline_device_count(const jpgpu_pipeline *p) { return !p ? 0u : (p->children.empty() ? 1u : (uint32_t)p->children.size()); }
@@ -1689,6 +1710,7 @@ static int multi_decode(jpgpu_pipeline *p, const uint8_t *const *data, const siz
         p->t.images_host_light += c->t.images_host_light;
         p->t.images_entry_pixels += c->t.images_entry_pixels;
         p->t.images_windowed += c->t.images_windowed;
+        p->t.images_resized += c->t.images_resized;
         p->t.input_pinned |= c->t.input_pinned;
     }
     p->t.decode_ms = t1 - t0;

@@ -1,0 +1,48 @@
+// resample.hip — the resample kernel of jpgpu_batch_create_resized (resample_band.hpp): one launch, every image of the batch in it.
+#include "resample_band.hpp"
+
+namespace jpgpu {
+
+// A 1-D grid numbered for the XCDs, as scaled_fused_kernel (kernels.hip): workgroups go to the 8 XCDs round-robin, so launch slot
+// s of XCD k is workgroup 8 s + k.  Image `image` takes XCD image % 8 and its bands are consecutive slots there: neighbouring bands
+// read overlapping source rows and the same tables, side by side in one L2.  A workgroup beyond its own image's bands leaves at once.
+__global__ __launch_bounds__(RS_NT, 4) void resample_band_kernel(const ResampleJob *__restrict__ jobs, const int32_t *__restrict__ tab_, uint32_t max_bands,
+                                                              uint32_t n_images) {
+    extern __shared__ __attribute__((aligned(16))) uint8_t lds_raw[];
+    const uint32_t xcd = blockIdx.x & 7u, slot = blockIdx.x >> 3, image = (slot / max_bands) * 8u + xcd, band = slot % max_bands;
+    if (image >= n_images) return;
+    const ResampleJob j = jobs[image];
+    if (band >= j.bands) return;  // (uniform)
+    const JP_GLOBAL int32_t *tab = (const JP_GLOBAL int32_t *)tab_;
+    const uint32_t chunks = RBand::chunks_of(j, tab, band), tid = threadIdx.x;
+    if (chunks == 1u) {  // (uniform) the band's source rows fit: one horizontal pass, every dword summed and stored
+        RBand::hpass(j, tab, band, 0u, 0u, j.out_w, tid, lds_raw);
+        __syncthreads();
+        RBand::vstore(j, tab, band, tid, lds_raw);
+        return;
+    }
+    const uint32_t groups = RBand::groups_of(j, band);
+    for (uint32_t group = 0; group < groups; group++) {
+        uint32_t x0, x1;
+        RBand::group_columns(j, band, group, x0, x1);
+        int32_t sum[4] = {0, 0, 0, 0};
+        for (uint32_t chunk = 0; chunk < chunks; chunk++) {
+            __syncthreads();  // (the vertical pass before has read its rows)
+            RBand::hpass(j, tab, band, chunk, x0, x1, tid, lds_raw);
+            __syncthreads();
+            RBand::vacc(j, tab, band, chunk, group, tid, lds_raw, sum);
+        }
+        RBand::vput(j, band, group, tid, sum);
+    }
+}
+
+hipError_t launch_resample_band(const ResampleJob *d_jobs, const int32_t *d_tab, uint32_t n_images, uint32_t max_bands, uint32_t lds_bytes, hipStream_t stream) {
+    if (n_images == 0 || max_bands == 0) return hipSuccess;
+    if (lds_bytes > RS_MAX_LDS) return hipErrorInvalidValue;
+    const uint64_t wgs = (((uint64_t)n_images + 7u) / 8u) * 8u * max_bands;
+    if (wgs > 0x7fffffffull) return hipErrorInvalidValue;
+    resample_band_kernel<<<dim3((uint32_t)wgs), dim3(RS_NT), lds_bytes, stream>>>(d_jobs, d_tab, max_bands, n_images);
+    return hipGetLastError();
+}
+
+}  // namespace jpgpu

@@ -1,0 +1,332 @@
+// resample_band.hpp — every image of a batch resampled to one output size (jpgpu_batch_create_resized) in ONE launch: the pixels the
+// batch's other kernels wrote (an image's window, or its whole output) in, out_h x out_w x nc bytes out, interleaved and packed.
+//
+// The arithmetic is the 8-bit integer bilinear resample with antialiasing of Pillow's Image.resize(size, BILINEAR) on the cropped
+// image (include/jpgpu.h): per axis a table of (xmin, n) and n 22-bit integer weights per output index, made on
+// the host in IEEE double (resample_coefficients below, = jpgpu_resample_coefficients); one pass is
+//     out = clamp((2^21 + sum p[xmin + x] * k[x]) >> 22, 0, 255)      (32-bit integers; the sum stays below 2^31)
+// the horizontal pass first, rounded to u8, the vertical pass on its result.  The device does integer work only.
+//
+//   1. planner (resample_plan, no HIP dependency: tests/emu runs it): a workgroup owns one image and a band of `rb` output rows.  The
+//      band's bytes are one run of the packed output (rows of out_w * nc bytes follow each other), cut into destination dwords.  The
+//      source rows a band needs ([ymin of its first row, ymax of its last)) go through LDS `cap_rows` at a time; `rb` is the largest
+//      band whose rows fit in one such chunk (RS_MAX_LDS).  A single output row whose support does not fit takes several chunks:
+//      RS_NT destination dwords at a time, every lane keeps the four sums of its dword in registers over the chunks.
+//   2. horizontal pass (RBand::hpass): one lane per (RS_HROWS source rows of the chunk, output column); the taps' bytes come from global memory
+//      as aligned dwords whatever the row's alignment (window rows of w * nc bytes start anywhere), neighbouring lanes read
+//      neighbouring / overlapping spans.  u8 rows of out_w * nc bytes (pitch rounded up to 4) into LDS.
+//   3. vertical pass (RBand::vpass): one lane per destination dword; where the dword's four bytes lie in one output row at a multiple
+//      of four (always when out_w * nc is one) the taps are aligned LDS dword reads, else byte reads.  Sums are exact in int32, so
+//      chunks add up in any order.
+//   4. store: whole aligned dwords; the first / last dword of a band that it shares with its neighbour byte by byte.
+#pragma once
+#include <stddef.h>
+#include <stdint.h>
+
+// (the tables and the planner need no HIP: image_job.cpp, a plain C++ translation unit, takes them from here)
+#if defined(__HIP__) || defined(JPGPU_HOST_EMULATION)
+#define JPGPU_RS_DEVICE_BODY 1
+#include "pixel_math.hpp"
+#endif
+
+namespace jpgpu {
+
+constexpr uint32_t RS_NT = 256;               // lanes per workgroup
+constexpr uint32_t RS_HROWS = 4;              // source rows a lane takes through the horizontal pass side by side (one column: the taps' weights
+                                              // are loaded once for them, their loads are independent of one another)
+constexpr uint32_t RS_MAX_LDS = 32u * 1024u;  // 5 workgroups share a CU's 160 kB
+constexpr uint32_t RS_MAX_OUT = 2048;         // largest output width / height
+constexpr uint32_t RS_PRECISION_BITS = 22;
+
+// ksize of an axis: ceil(max(in / out, 1)) * 2 + 1
+inline uint32_t resample_ksize(uint32_t in_size, uint32_t out_size) {
+    const double scale = (double)in_size / (double)out_size;
+    const double fs = scale < 1.0 ? 1.0 : scale;
+    uint32_t c = (uint32_t)fs;
+    if ((double)c < fs) c++;
+    return c * 2u + 1u;
+}
+
+// The tables of one axis: bounds[2 xx] = xmin, bounds[2 xx + 1] = n, coefs[xx * ksize + x] = k[x] (zero beyond n).  IEEE double, the
+// operations in the order of the statement in DESIGN.md §4.10 (one operation per statement: nothing for a compiler to contract).
+inline void resample_coefficients(uint32_t in_size, uint32_t out_size, int32_t *bounds, int32_t *coefs, uint32_t ksize) {
+    const double scale = (double)in_size / (double)out_size;
+    const double fs = scale < 1.0 ? 1.0 : scale;
+    const double support = fs;
+    const double ss = 1.0 / fs;
+    for (uint32_t xx = 0; xx < out_size; xx++) {
+        const double center = ((double)xx + 0.5) * scale;
+        int32_t xmin = (int32_t)(center - support + 0.5);
+        if (xmin < 0) xmin = 0;
+        int32_t xmax = (int32_t)(center + support + 0.5);
+        if (xmax > (int32_t)in_size) xmax = (int32_t)in_size;
+        const int32_t n = xmax - xmin;
+        int32_t *k = coefs + (size_t)xx * ksize;
+        double ww = 0.0;
+        for (int32_t x = 0; x < n; x++) {
+            double a = (double)(x + xmin) - center;
+            a = a + 0.5;
+            a = a * ss;
+            if (a < 0.0) a = -a;
+            const double w = a < 1.0 ? 1.0 - a : 0.0;
+            ww = ww + w;
+        }
+        for (int32_t x = 0; x < (int32_t)ksize; x++) {
+            if (x >= n) {
+                k[x] = 0;
+                continue;
+            }
+            double a = (double)(x + xmin) - center;
+            a = a + 0.5;
+            a = a * ss;
+            if (a < 0.0) a = -a;
+            const double w = a < 1.0 ? 1.0 - a : 0.0;
+            double v = ww != 0.0 ? w / ww : w;
+            v = v * (double)(1 << RS_PRECISION_BITS);
+            k[x] = (int32_t)(v + 0.5);
+        }
+        bounds[2 * xx] = xmin, bounds[2 * xx + 1] = n;
+    }
+}
+
+// One image of the launch.  Table offsets count int32 words from the launch's table base.
+struct ResampleJob {
+    const uint8_t *src;  // in_h rows of in_w * nc bytes, packed
+    uint8_t *dst;        // out_h rows of out_w * nc bytes, packed; 4-byte aligned
+    uint32_t in_w, in_h, nc, out_w, out_h;
+    uint32_t hb, hk, hks;  // horizontal bounds / coefficients / ksize
+    uint32_t vb, vk, vks;  // vertical
+    uint32_t rb, bands;    // output rows per band, bands
+    uint32_t cap_rows;     // source rows per LDS chunk
+    uint32_t pitch;        // LDS row pitch: out_w * nc rounded up to 4
+    uint32_t lds_bytes;    // cap_rows * pitch
+};
+
+// Plans the bands of a job whose sizes and table offsets are set and whose tables (`tab`, host copy) are filled.  False for sizes the
+// kernel does not run (the batch refuses them before).
+inline bool resample_plan(ResampleJob &j, const int32_t *tab, uint32_t lds_cap = RS_MAX_LDS, uint32_t rb_cap = 64u) {
+    if (j.nc == 0 || j.nc > 4 || j.in_w == 0 || j.in_h == 0 || j.out_w == 0 || j.out_h == 0 || j.out_w > RS_MAX_OUT || j.out_h > RS_MAX_OUT) return false;
+    const uint32_t rowb = j.out_w * j.nc;
+    j.pitch = (rowb + 3u) & ~3u;
+    if (lds_cap > RS_MAX_LDS) lds_cap = RS_MAX_LDS;
+    j.cap_rows = lds_cap / j.pitch;
+    if (j.cap_rows == 0) return false;
+    if (j.cap_rows > j.in_h) j.cap_rows = j.in_h;
+    j.lds_bytes = j.cap_rows * j.pitch;
+    const int32_t *vb = tab + j.vb;
+    uint32_t rb = rb_cap ? rb_cap : 1u;
+    if (rb > j.out_h) rb = j.out_h;
+    for (; rb > 1u; rb--) {  // the largest band whose source rows fit in one chunk, for every band
+        bool ok = true;
+        for (uint32_t r0 = 0; r0 < j.out_h && ok; r0 += rb) {
+            const uint32_t r1 = r0 + rb < j.out_h ? r0 + rb : j.out_h;
+            const uint32_t s0 = (uint32_t)vb[2 * r0], s1 = (uint32_t)(vb[2 * (r1 - 1u)] + vb[2 * (r1 - 1u) + 1]);
+            ok = s1 - s0 <= j.cap_rows;
+        }
+        if (ok) break;
+    }
+    j.rb = rb;
+    j.bands = (j.out_h + rb - 1u) / rb;
+    return true;
+}
+
+#ifdef JPGPU_RS_DEVICE_BODY
+struct RBand {
+    // the band's output rows [r0, r1) and its source rows [s0, s1)
+    static __device__ __forceinline__ void rows_of(const ResampleJob &j, const JP_GLOBAL int32_t *tab, uint32_t band, uint32_t &r0, uint32_t &r1, uint32_t &s0,
+                                                   uint32_t &s1) {
+        r0 = band * j.rb;
+        r1 = min(r0 + j.rb, j.out_h);
+        const JP_GLOBAL int32_t *vb = tab + j.vb;
+        s0 = (uint32_t)vb[2u * r0];
+        s1 = (uint32_t)(vb[2u * (r1 - 1u)] + vb[2u * (r1 - 1u) + 1u]);
+    }
+    static __device__ __forceinline__ uint32_t chunks_of(const ResampleJob &j, const JP_GLOBAL int32_t *tab, uint32_t band) {
+        uint32_t r0, r1, s0, s1;
+        rows_of(j, tab, band, r0, r1, s0, s1);
+        return (s1 - s0 + j.cap_rows - 1u) / j.cap_rows;
+    }
+    // the band's run of destination bytes [a, b) (offsets from dst) and its dwords [q0, q1)
+    static __device__ __forceinline__ void run_of(const ResampleJob &j, uint32_t band, uint32_t &a, uint32_t &b, uint32_t &q0, uint32_t &q1) {
+        const uint32_t rowb = j.out_w * j.nc, r0 = band * j.rb, r1 = min(r0 + j.rb, j.out_h);
+        a = r0 * rowb, b = r1 * rowb;
+        q0 = a >> 2, q1 = (b + 3u) >> 2;
+    }
+    // groups of RS_NT destination dwords in the band (the chunked path takes them one at a time)
+    static __device__ __forceinline__ uint32_t groups_of(const ResampleJob &j, uint32_t band) {
+        uint32_t a, b, q0, q1;
+        run_of(j, band, a, b, q0, q1);
+        return (q1 - q0 + RS_NT - 1u) / RS_NT;
+    }
+    // the output columns [x0, x1) whose horizontal pass group `group` of the band needs: a band of one row needs only the columns of
+    // the group's own bytes (the chunked path repeats the pass per group), a taller one every column
+    static __device__ __forceinline__ void group_columns(const ResampleJob &j, uint32_t band, uint32_t group, uint32_t &x0, uint32_t &x1) {
+        x0 = 0u, x1 = j.out_w;
+        if (j.rb != 1u) return;
+        uint32_t a, b, q0, q1;
+        run_of(j, band, a, b, q0, q1);
+        const uint32_t f0 = max(4u * (q0 + group * RS_NT), a), f1 = min(4u * (q0 + (group + 1u) * RS_NT), b);
+        if (f0 >= f1) return;
+        x0 = (f0 - a) / j.nc, x1 = (f1 - a + j.nc - 1u) / j.nc;
+    }
+
+    // horizontal pass: columns [x0, x1) of the chunk's source rows [c0, c1) into LDS row (s - c0)
+    static __device__ __forceinline__ void hpass(const ResampleJob &j, const JP_GLOBAL int32_t *tab, uint32_t band, uint32_t chunk, uint32_t x0, uint32_t x1,
+                                                 uint32_t tid, uint8_t *lds) {
+        uint32_t r0, r1, s0, s1;
+        rows_of(j, tab, band, r0, r1, s0, s1);
+        const uint32_t c0 = s0 + chunk * j.cap_rows, c1 = min(c0 + j.cap_rows, s1);
+        if (c0 >= c1 || x0 >= x1) return;
+        const uint32_t nc = j.nc, nx = x1 - x0, nrows = c1 - c0, units = ((nrows + RS_HROWS - 1u) / RS_HROWS) * nx;
+        const size_t src_pitch = (size_t)j.in_w * nc;
+        const JP_GLOBAL int32_t *hb = tab + j.hb;
+        const JP_GLOBAL int32_t *hk = tab + j.hk;
+        const JP_GLOBAL uint8_t *src = (const JP_GLOBAL uint8_t *)j.src;
+#pragma unroll 1
+        for (uint32_t u = tid; u < units; u += RS_NT) {
+            const uint32_t rg = u / nx, xx = x0 + (u - rg * nx), row0 = rg * RS_HROWS;
+            const uint32_t xmin = (uint32_t)hb[2u * xx], n = (uint32_t)hb[2u * xx + 1u];
+            const JP_GLOBAL int32_t *k = hk + (size_t)xx * j.hks;
+            // the span's bytes of every row as aligned dwords, whatever the row's alignment (a row beyond the chunk reads the chunk's last)
+            const JP_GLOBAL uint32_t *pd[RS_HROWS];
+            uint32_t cur[RS_HROWS], pos[RS_HROWS];
+            int32_t sum[RS_HROWS][4];
+#pragma unroll
+            for (uint32_t i = 0; i < RS_HROWS; i++) {
+                const uint32_t row = min(row0 + i, nrows - 1u);
+                const JP_GLOBAL uint8_t *p = src + (size_t)(c0 + row) * src_pitch + (size_t)xmin * nc;
+                const uint32_t m = (uint32_t)(uintptr_t)p & 3u;
+                pd[i] = reinterpret_cast<const JP_GLOBAL uint32_t *>(p - m);
+                pos[i] = m;
+#pragma unroll
+                for (uint32_t c = 0; c < 4; c++) sum[i][c] = 1 << (RS_PRECISION_BITS - 1);
+            }
+#pragma unroll
+            for (uint32_t i = 0; i < RS_HROWS; i++) cur[i] = *pd[i];
+            for (uint32_t x = 0; x < n; x++) {
+                const int32_t kx = k[x];
+#pragma unroll
+                for (uint32_t c = 0; c < 4; c++)
+                    if (c < nc) {
+#pragma unroll
+                        for (uint32_t i = 0; i < RS_HROWS; i++) {
+                            if (pos[i] == 4u) {
+                                pd[i]++;
+                                cur[i] = *pd[i];
+                                pos[i] = 0u;
+                            }
+                            sum[i][c] += (int32_t)((cur[i] >> (8u * pos[i])) & 255u) * kx;
+                            pos[i]++;
+                        }
+                    }
+            }
+#pragma unroll
+            for (uint32_t i = 0; i < RS_HROWS; i++) {
+                if (row0 + i >= nrows) continue;
+                uint8_t *o = lds + (row0 + i) * j.pitch + xx * nc;
+#pragma unroll
+                for (uint32_t c = 0; c < 4; c++)
+                    if (c < nc) {
+                        int32_t v = sum[i][c] >> RS_PRECISION_BITS;
+                        v = v < 0 ? 0 : (v > 255 ? 255 : v);
+                        o[c] = (uint8_t)v;
+                    }
+            }
+        }
+    }
+
+    // the share of source rows [c0, c1) (in LDS) in the four sums of destination dword q: where its bytes lie in one output row at a
+    // multiple of four an aligned LDS dword per tap, else byte by byte
+    static __device__ __forceinline__ void item_sum(const ResampleJob &j, const JP_GLOBAL int32_t *tab, uint32_t q, uint32_t a, uint32_t b, uint32_t c0,
+                                                    uint32_t c1, const uint8_t *lds, int32_t (&sum)[4]) {
+        const uint32_t rowb = j.out_w * j.nc;
+        const JP_GLOBAL int32_t *vb = tab + j.vb;
+        const JP_GLOBAL int32_t *vk = tab + j.vk;
+        const uint32_t f0 = max(4u * q, a), f1 = min(4u * q + 4u, b);  // the dword's bytes inside the band
+        const uint32_t row0 = f0 / rowb, col0 = f0 - row0 * rowb;
+        if (f1 - f0 == 4u && col0 + 4u <= rowb && (col0 & 3u) == 0u) {
+            const uint32_t ymin = (uint32_t)vb[2u * row0], n = (uint32_t)vb[2u * row0 + 1u];
+            const uint32_t t0 = c0 > ymin ? c0 - ymin : 0u, t1 = min(n, c1 > ymin ? c1 - ymin : 0u);
+            const JP_GLOBAL int32_t *k = vk + (size_t)row0 * j.vks;
+            for (uint32_t t = t0; t < t1; t++) {
+                const uint32_t d = *reinterpret_cast<const uint32_t *>(lds + (ymin + t - c0) * j.pitch + col0);
+                const int32_t kt = k[t];
+                sum[0] += (int32_t)(d & 255u) * kt;
+                sum[1] += (int32_t)((d >> 8) & 255u) * kt;
+                sum[2] += (int32_t)((d >> 16) & 255u) * kt;
+                sum[3] += (int32_t)(d >> 24) * kt;
+            }
+            return;
+        }
+#pragma unroll
+        for (uint32_t e = 0; e < 4; e++) {
+            const uint32_t f = 4u * q + e;
+            if (f < f0 || f >= f1) continue;
+            const uint32_t row = f / rowb, col = f - row * rowb;
+            const uint32_t ymin = (uint32_t)vb[2u * row], n = (uint32_t)vb[2u * row + 1u];
+            const uint32_t t0 = c0 > ymin ? c0 - ymin : 0u, t1 = min(n, c1 > ymin ? c1 - ymin : 0u);
+            const JP_GLOBAL int32_t *k = vk + (size_t)row * j.vks;
+            int32_t s = 0;
+            for (uint32_t t = t0; t < t1; t++) s += (int32_t)lds[(ymin + t - c0) * j.pitch + col] * k[t];
+            sum[e] += s;
+        }
+    }
+    // the sums rounded, clamped and stored: a whole dword where all four bytes are the band's, else its own bytes one by one (the
+    // first / last dword of a band may be shared with its neighbour)
+    static __device__ __forceinline__ void item_store(const ResampleJob &j, uint32_t q, uint32_t a, uint32_t b, const int32_t (&sum)[4]) {
+        JP_GLOBAL uint8_t *dst = (JP_GLOBAL uint8_t *)j.dst;
+        uint32_t v[4];
+#pragma unroll
+        for (uint32_t e = 0; e < 4; e++) {
+            const int32_t s = (sum[e] + (1 << (RS_PRECISION_BITS - 1))) >> RS_PRECISION_BITS;
+            v[e] = (uint32_t)(s < 0 ? 0 : (s > 255 ? 255 : s));
+        }
+        if (4u * q >= a && 4u * q + 4u <= b) {
+            reinterpret_cast<JP_GLOBAL uint32_t *>(dst)[q] = v[0] | (v[1] << 8) | (v[2] << 16) | (v[3] << 24);
+        } else {
+#pragma unroll
+            for (uint32_t e = 0; e < 4; e++)
+                if (4u * q + e >= a && 4u * q + e < b) dst[4u * q + e] = (uint8_t)v[e];
+        }
+    }
+
+    // vertical pass of a band whose source rows are one chunk: every destination dword summed and stored
+    static __device__ __forceinline__ void vstore(const ResampleJob &j, const JP_GLOBAL int32_t *tab, uint32_t band, uint32_t tid, const uint8_t *lds) {
+        uint32_t r0, r1, s0, s1, a, b, q0, q1;
+        rows_of(j, tab, band, r0, r1, s0, s1);
+        run_of(j, band, a, b, q0, q1);
+#pragma unroll 1
+        for (uint32_t q = q0 + tid; q < q1; q += RS_NT) {
+            int32_t sum[4] = {0, 0, 0, 0};
+            item_sum(j, tab, q, a, b, s0, s1, lds, sum);
+            item_store(j, q, a, b, sum);
+        }
+    }
+    // the chunked path: dword `tid` of group `group` gathers its sums (exact in int32) chunk by chunk in registers, then stores
+    static __device__ __forceinline__ void vacc(const ResampleJob &j, const JP_GLOBAL int32_t *tab, uint32_t band, uint32_t chunk, uint32_t group, uint32_t tid,
+                                                const uint8_t *lds, int32_t (&sum)[4]) {
+        uint32_t r0, r1, s0, s1, a, b, q0, q1;
+        rows_of(j, tab, band, r0, r1, s0, s1);
+        run_of(j, band, a, b, q0, q1);
+        const uint32_t c0 = s0 + chunk * j.cap_rows, c1 = min(c0 + j.cap_rows, s1), q = q0 + group * RS_NT + tid;
+        if (q < q1 && c0 < c1) item_sum(j, tab, q, a, b, c0, c1, lds, sum);
+    }
+    static __device__ __forceinline__ void vput(const ResampleJob &j, uint32_t band, uint32_t group, uint32_t tid, const int32_t (&sum)[4]) {
+        uint32_t a, b, q0, q1;
+        run_of(j, band, a, b, q0, q1);
+        const uint32_t q = q0 + group * RS_NT + tid;
+        if (q < q1) item_store(j, q, a, b, sum);
+    }
+};
+
+#endif  // JPGPU_RS_DEVICE_BODY
+
+}  // namespace jpgpu
+
+#if defined(__HIP__) && !defined(JPGPU_HOST_EMULATION)
+#include <hip/hip_runtime.h>
+namespace jpgpu {
+// resample.hip: n_images jobs, their tables from d_tab; max_bands / lds_bytes over the jobs
+hipError_t launch_resample_band(const ResampleJob *d_jobs, const int32_t *d_tab, uint32_t n_images, uint32_t max_bands, uint32_t lds_bytes, hipStream_t stream);
+}  // namespace jpgpu
+#endif

@@ -9,7 +9,7 @@ import ctypes as C
 import numpy as np
 
 from . import _native as N
-from .batch import window_structs
+from .batch import output_size_pair, window_structs
 from .decoder import CODING_PROCESSES, PIXEL_FORMATS, ImageInfo
 from .error import check, error_for_status
 from .worker import color_transform_id
@@ -75,7 +75,7 @@ class Pipeline:
     __del__ = close
 
     def decode(self, streams, download=True, dense=False, device_entropy=True, scale=None, color_transform=None, max_decoding_buffer_size=None,
-               gather=False, host_light=None, input_pinned=False, progressive_on_host=False, windows=None):
+               gather=False, host_light=None, input_pinned=False, progressive_on_host=False, windows=None, output_size=None):
         """-> list with, per stream, a numpy uint8 array of the decoded pixels (``Decoder.decode()``'s Vec<u8>) or the
         ``Error`` instance that stream produced.  download=False leaves the pixels in HBM (see ``device_pointer``); dense=True sends all
         64 coefficients of every block over PCIe instead of the compact form (same pixels, A/B switch); device_entropy=True
@@ -93,7 +93,12 @@ class Pipeline:
         the stream's pixels are then that slice of its whole decode, packed — ``full.reshape(H, W, nc)[y:y+h, x:x+w]``
         (``full.reshape(H, nc, W)[y:y+h, :, x:x+w]`` for color_transform "None" with more than one component) — in the pixel grid of the
         image's output, i.e. after `scale`.  A window outside its image fails that stream alone (FormatError in the result list);
-        ``window(i)`` gives the window decoded, ``info(i)`` keeps the image's size.  The arrays stay flat uint8."""
+        ``window(i)`` gives the window decoded, ``info(i)`` keeps the image's size.  The arrays stay flat uint8.
+        output_size: None or (w, h), each 1..2048 (jpgpu_pipeline_set_output_size, set on every call like the scale): every stream's pixels
+        are the 8-bit bilinear resample with antialiasing (Pillow's ``Image.resize((w, h), BILINEAR)`` arithmetic on the cropped image,
+        DESIGN.md §4.10) of what it gives without — its window or its whole output — so every array is h * w * nc bytes and only those
+        cross the link; a stream with planar output (color_transform "None", more than one component) fails alone (UnsupportedError);
+        ``timings()["images_resized"]`` counts the streams."""
         if isinstance(streams, PinnedFiles):
             bufs = None
             n = len(streams)
@@ -103,10 +108,13 @@ class Pipeline:
             bufs = [bytes(s.read() if hasattr(s, "read") else s) for s in streams]
             n = len(bufs)
         wins = window_structs(windows, n)  # (raises on a list of the wrong length, before anything native is called)
+        size = (0, 0) if output_size is None else output_size_pair(output_size)
         L = N.lib()
         check(L.jpgpu_pipeline_set_max_decoding_buffer_size(self._h, (1 << 64) - 1 if max_decoding_buffer_size is None else int(max_decoding_buffer_size)), b"set_max")
         check(L.jpgpu_pipeline_set_color_transform(self._h, color_transform_id(color_transform) if color_transform is not None else -1), b"set_color_transform")
         check(L.jpgpu_pipeline_set_scale(self._h, *((int(scale[0]), int(scale[1])) if scale else (0, 0))), b"set_scale")
+        st = L.jpgpu_pipeline_set_output_size(self._h, *size)
+        check(st, L.jpgpu_pipeline_last_error(self._h) if st else b"")
         if bufs is None:
             ptrs = (C.c_void_p * max(n, 1))(*[streams.base + o for o in streams.offsets])
             lens = (C.c_size_t * max(n, 1))(*streams.lengths)
