@@ -49,7 +49,7 @@ int batch_upload_compact(jpgpu_batch *b, uint32_t image, uint32_t comp, const vo
 // mapped block itself (huff.hip, launch_copy_to_host); falls back to the copy engine if the block has no device mapping
 int copy_device_to_pinned_host(void *host_pinned, const void *d_src, size_t bytes, void *hip_stream);
 
-// Windows per image ahead of jpgpu_batch_create_windowed (batch.cpp): is `wn` a window on `d` (windowed), no window (empty, or the
+// Windows per image ahead of jpgpu_batch_create_windowed (window_rule, batch_layout.hpp): is `wn` a window on `d` (windowed), no window (empty, or the
 // whole gw x gh output grid), outside the grid (JPGPU_ERR_FORMAT) or refused by the window planner (JPGPU_ERR_UNSUPPORTED)?
 int batch_check_window(const jpgpu_image_desc &d, const jpgpu_window &wn, bool &windowed, uint32_t &gw, uint32_t &gh, std::string &why);
 uint32_t batch_windowed_images(const jpgpu_batch *b);  // images of the batch in the window group
@@ -62,7 +62,7 @@ size_t batch_out_arena_bound(const jpgpu_batch *b);  // jpgpu_batch_out_arena_by
 void worker_recycle(jpgpu_worker *w);
 
 
-// ---- device entropy decoding of restart-marker streams (huff_core.hpp), used by the pipeline ----------------------
+// ---- device entropy decoding of restart-marker streams (huff_core.hpp, batch_entropy.cpp), used by the pipeline ----
 namespace host {
 struct PlannedScan;
 struct ProgPlan;
@@ -118,7 +118,7 @@ int batch_device_progressive_launch(jpgpu_batch *b, const DeviceProgressiveImage
                                     const std::function<void(uint32_t, const std::function<void(uint32_t)> &)> *par = nullptr,
                                     void *copy_stream = nullptr, DeviceScratch *scratch = nullptr, bool pipelined = true);
 bool batch_progressive_kernel_ms(jpgpu_batch *b, float *ms);  // duration of the last launch's track kernel (events; stream synchronised)
-bool batch_phase_times(jpgpu_batch *b, float ms[4]);  // JPGPU_BATCH_KERNEL_TIMES, batch.cpp
+bool batch_phase_times(jpgpu_batch *b, float ms[4]);  // JPGPU_BATCH_KERNEL_TIMES, batch_entropy.cpp
 bool batch_phase_stamps(jpgpu_batch *ref, jpgpu_batch *b, float ms[6]);  // (+ JPGPU_PIPE_TRACE) event times relative to ref's first event
 
 }  // namespace jpgpu

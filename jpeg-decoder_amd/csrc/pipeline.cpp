@@ -20,6 +20,7 @@
 #include <thread>
 #include <vector>
 
+#include "batch_layout.hpp"
 #include "compact.hpp"
 #include "host/frontend.hpp"
 #include "host_common.hpp"
@@ -344,7 +345,7 @@ static const jpgpu_pipeline *child_of(const jpgpu_pipeline *p, uint32_t &image) 
 }
 static int multi_decode(jpgpu_pipeline *p, const uint8_t *const *data, const size_t *len, const jpgpu_window *windows, uint32_t n, uint32_t flags);
 // Up to how many scans does a call walk its progressive frames a WAVE per scan (pipelined, huff_prog_job.hpp)?  Always: the launch
-// order keeps a frame's waves on one XCD, producers in front (csrc/batch.cpp), so an oversubscribed launch cannot starve a producer
+// order keeps a frame's waves on one XCD, producers in front (csrc/batch_entropy.cpp), so an oversubscribed launch cannot starve a producer
 // (round 5's lanes had to fit the device at once).  Beyond the limit: a wave per TRACK, its scans one after the other —
 // JPGPU_PROG_LANES_MAX (tests, A/B; read per call) / JPGPU_PROG_SERIAL.
 static uint64_t prog_lanes_max() {
@@ -896,7 +897,7 @@ int jpgpu_pipeline_decode_windowed(jpgpu_pipeline *p, const uint8_t *const *data
             // (a sub-batch with windows: a quarter more than these windows need, at most what the whole images take — the totals of a
             // loader's fresh random crops differ little from call to call, and pinning memory anew costs milliseconds)
             const size_t need = jpgpu_batch_out_arena_bytes(sb.batch);
-            sb.h_out_bytes = sb.wins.empty() ? need : std::max(need, std::min(jpgpu::batch_out_arena_bound(sb.batch), need + need / 4));
+            sb.h_out_bytes = sb.wins.empty() ? need : jpgpu::arena_headroom(need, jpgpu::batch_out_arena_bound(sb.batch));
             P_HIP(hipHostMalloc((void **)&sb.h_out, sb.h_out_bytes, hipHostMallocDefault));
         }
         if (s0 != 0.0) fprintf(stderr, "pipeline trace: sub-batch %u (%zu images, %zu with a window): %s in %.2f ms\n", j, descs.size(), (size_t)jpgpu::batch_windowed_images(sb.batch), how, now_ms() - s0);

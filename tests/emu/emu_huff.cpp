@@ -130,7 +130,7 @@ int emu_huff_plan(const uint8_t* data, size_t len, jpgpu_image_desc* desc, uint3
     for (auto& s : scans) *n_segments += (uint32_t)(s.seg_off.size() / 2);
     return 0;
 }
-// 1: every scan writes all blocks of its planes (huff_scan_covers_planes: batch.cpp skips the zero fill for such images)
+// 1: every scan writes all blocks of its planes (huff_scan_covers_planes: batch_entropy.cpp skips the zero fill for such images)
 int emu_huff_covered(const uint8_t* data, size_t len) {
     Frontend fe(data, len);
     std::vector<PlannedScan> scans;
@@ -257,7 +257,7 @@ extern "C" int emu_huff_decode(const uint8_t* data, size_t len, int16_t* const* 
     uint32_t status = 0;
     HuffRange rg;  // what the kernels fold per wave and raise in the image's statistics words
     for (const PlannedScan& ps : scans) {
-        // staging as batch.cpp does it: every segment unstuffed into its own 16-byte aligned, zero padded slot
+        // staging as batch_entropy.cpp does it: every segment unstuffed into its own 16-byte aligned, zero padded slot
         size_t total = 0;
         for (size_t sg = 0; sg + 1 < ps.seg_off.size(); sg += 2) total += huff_slot_bytes(ps.seg_off[sg + 1] - ps.seg_off[sg]);
         std::vector<uint8_t> stage_raw(total + 16);
@@ -270,10 +270,10 @@ extern "C" int emu_huff_decode(const uint8_t* data, size_t len, int16_t* const* 
             table[sg] = o;
             table[sg + 1] = huff_stage_segment(stage + o, data + ps.data_off + first, n, ps.check_at_staging ? &clean : nullptr);
             o += huff_slot_bytes(n);
-            if (!clean) status |= 1u | 16u;  // (batch.cpp: the staging pass refuses the stream)
+            if (!clean) status |= 1u | 16u;  // (batch_entropy.cpp: the staging pass refuses the stream)
         }
         if (status & 1u) continue;
-        // restart-marker streams (batch.cpp, dri_geom): every segment in chunk slots of its own; one segment = a scan without markers
+        // restart-marker streams (batch_entropy.cpp, dri_geom): every segment in chunk slots of its own; one segment = a scan without markers
         const bool dri_chunked = ps.ri != 0 && ps.seg_off.size() >= 4;
         {  // the self-synchronising chunk decoder, passes run one after the other
             HuffSyncLds* S = new HuffSyncLds;
@@ -407,7 +407,7 @@ extern "C" int emu_huff_decode(const uint8_t* data, size_t len, int16_t* const* 
                 g_emit_mismatch = 0;
                 emu_expand(sj, rg);
                 if (g_emit_mismatch) status |= 0x4000u;  // entries that name another component than the block numbering does
-                // the entry-list walk's reading of the same lists (batch.cpp's eligibility rule): strips of 42, 3 and 1 MCUs
+                // the entry-list walk's reading of the same lists (batch_entropy.cpp's eligibility rule): strips of 42, 3 and 1 MCUs
                 bool walk = ps.ncomp == 3 && !sj.uniform && sj.bpm == 6u && scans.size() == 1 && sj.n_mcu % sj.cols == 0;
                 for (uint32_t c = 0; walk && c < 3; c++)
                     walk = ps.comp[c].frame_index == c && ps.comp[c].h == (c ? 1u : 2u) && ps.comp[c].v == (c ? 1u : 2u);

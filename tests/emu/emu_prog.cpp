@@ -70,7 +70,7 @@ int emu_prog_decode(const uint8_t *data, size_t len, int16_t *const planes[4], i
     const uint32_t nc = fe.ncomp();
     std::vector<std::vector<uint64_t>> masks(nc);
     for (uint32_t c = 0; c < nc; c++) masks[c].assign((size_t)fe.components()[c].block_width * fe.components()[c].block_height * 2u, 0);
-    // staging: every scan unstuffed into its own slot (huff_stage_segment), as batch.cpp does
+    // staging: every scan unstuffed into its own slot (huff_stage_segment), as batch_entropy.cpp does
     std::vector<std::vector<uint8_t>> slots(plan.scans.size());
     std::vector<ProgScan> scans(plan.scans.size());
     uint32_t status = 0;

@@ -32,7 +32,7 @@ def _device(data):
     if L.emu_huff_plan(buf, len(data), C.byref(desc), C.byref(ns), C.byref(nseg)) != 0:
         return None
     # the expansion writes every block of a scan whole, so the planes of a stream whose scans cover their planes may start as
-    # anything — a pattern here; other planes start as zeros (batch.cpp's fill)
+    # anything — a pattern here; other planes start as zeros (batch_entropy.cpp's fill)
     fill = 0x5A5A if L.emu_huff_covered(buf, len(data)) == 1 else 0
     planes = [np.full(desc.components[c].block_width * desc.components[c].block_height * 64, fill, np.int16) for c in range(desc.ncomp)]
     ptrs = (C.c_void_p * 4)(*([p.ctypes.data for p in planes] + [None] * (4 - len(planes))))

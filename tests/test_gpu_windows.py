@@ -236,3 +236,75 @@ def test_windows_at_every_scale_share_one_launch_grid():
     assert path == "window"
     for i, (case, win) in enumerate(zip(cases, wins)):
         assert np.array_equal(outs[i], _want(case, _full(case), win)), (i, case[4], case[5], win)
+
+
+# ---- every launch group in one batch, on a caller's arenas, bound anew ------------------------------------------------------------------
+_GROUPS = [  # (sampling, colour transform, scale, window): gray in front of colour, so the second image's first_plane_job is 1
+    ([(1, 1)], "Grayscale", 8, None), ([(2, 2), (1, 1), (1, 1)], "YCbCr", 8, None),                    # fused (two plans)
+    ([(1, 1)], "Grayscale", 2, None), ([(1, 1)] * 3, "YCbCr", 4, None),                                # scaled
+    ([(1, 1)], "Grayscale", 4, (3, 5, 21, 13)), ([(2, 2), (1, 1), (1, 1)], "YCbCr", 8, (7, 3, 45, 31)),  # window
+    ([(3, 1), (1, 1), (1, 1)], "YCbCr", 8, None), ([(3, 1), (1, 1), (1, 1)], "YCbCr", 8, None),        # generic: no fused kernel takes 3x1
+    ([(1, 1)] * 3, "None", 8, None), ([(1, 1)] * 4, "None", 8, None)]                                # planar output (no output size)
+_NEW_TABLES = (1, 2, 5, 6, 9)  # one image of each group gets other quantization tables in the second round
+
+
+def _rebound_rounds(n_images, size):
+    """Two rounds on one batch: decode on a first pair of caller-owned arenas; then other arenas, other pictures, other tables."""
+    import resample_ref as R
+
+    hip = _hip()
+    rng = np.random.default_rng(83 * 59 + n_images)
+    groups = _GROUPS[:n_images]
+    first = [_case(rng, 83 + 2 * (i % 3), 59 + 2 * (i % 2), samp, ct, scale, "sparse") for i, (samp, ct, scale, _w) in enumerate(groups)]
+    second = []
+    for i, (oc, qts, _c, ct, ow, oh) in enumerate(first):
+        _oc, new_q, coefs, *_r = _case(rng, 83 + 2 * (i % 3), 59 + 2 * (i % 2), groups[i][0], ct, groups[i][2], "sparse")
+        second.append((oc, new_q if i in _NEW_TABLES else qts, coefs, ct, ow, oh))
+    wins = [g[3] for g in groups]
+
+    def want(case, win):
+        if size is None:
+            return _want(case, _full(case), win)
+        oc, *_r, ow, oh = case
+        W, H = grid_of(oc, ow, oh)
+        x, y, w, h = win or (0, 0, W, H)
+        src = window_slice(_full(case), W, H, len(oc), case[3], (x, y, w, h)).reshape(h, w, len(oc))
+        return R.resize(src, size[0], size[1]).reshape(-1)
+
+    b = J.Batch([_desc(c) for c in first], flags=J._native.BATCH_EXTERNAL_BUFFERS, windows=wins, output_size=size)
+    nco, nout = b.coef_arena_bytes(), b.out_arena_bytes()
+    arenas = [C.c_void_p() for _ in range(4)]
+    try:
+        assert b.path == ("mixed" if size is None else "mixed+resize")
+        for a, nbytes in zip(arenas, (nco, nout, nco, nout)):
+            assert hip.hipMalloc(C.byref(a), nbytes) == 0 and hip.hipMemset(a, 0x5A, nbytes) == 0
+        outs = []
+        for rnd, cases in enumerate((first, second)):
+            b.bind(arenas[2 * rnd].value, arenas[2 * rnd + 1].value)
+            for i, (oc, qts, coefs, *_r) in enumerate(cases):
+                for c in range(len(oc)):
+                    if rnd == 1 and i in _NEW_TABLES:
+                        b.set_quantization_table(i, c, qts[c])
+                    b.upload(i, c, coefs[c])
+            b.decode()
+            b.synchronize()
+            outs.append([b.download(i) for i in range(n_images)])
+            for i, case in enumerate(cases):
+                w_ = want(case, wins[i])
+                assert outs[rnd][i].size == w_.size and np.array_equal(outs[rnd][i], w_), (size, rnd, i, np.nonzero(outs[rnd][i] != w_)[0][:10].tolist())
+        for i in range(n_images):
+            assert not np.array_equal(outs[0][i], outs[1][i]), (size, i)
+    finally:
+        b.close()
+        for a in arenas:
+            hip.hipFree(a)
+
+
+def test_every_launch_group_in_one_batch_rebound():
+    """Two images of every launch group — the fused plans, the scaled, the window and the generic group — and two planar ones in ONE
+    batch, each about 83 x 59 (several MCUs across and down, odd sizes), a gray image in front of a colour one inside each group:
+    every image equals the oracle's decode (sliced where windowed); after other arenas are bound, other pictures uploaded and another
+    quantization table set on one image of each group, every image equals the oracle again and differs from before.  The same with
+    an output size for the eight images with interleaved output, against tests/resample_ref.py."""
+    _rebound_rounds(10, None)
+    _rebound_rounds(8, (40, 30))

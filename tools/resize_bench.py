@@ -37,7 +37,7 @@ import window_bench as WB  # noqa: E402
 
 W, H, N = WB.W, WB.H, WB.N
 SIZE = (224, 224)
-SOURCES = ("resample_band.hpp", "resample.hip", "window_band.hpp", "window.hip", "batch.cpp", "pipeline.cpp")
+SOURCES = ("resample_band.hpp", "resample.hip", "window_band.hpp", "window.hip", "batch.cpp", "batch_internal.hpp", "batch_layout.hpp", "batch_entropy.cpp", "pipeline.cpp")
 
 
 def header(tool, args):

@@ -80,7 +80,7 @@ def varied(rng, n, frac, aligned):
     return out
 
 
-def sources_sha256(files=("window_band.hpp", "window.hip", "batch.cpp")):
+def sources_sha256(files=("window_band.hpp", "window.hip", "batch.cpp", "batch_internal.hpp", "batch_layout.hpp")):
     """sha256 over the window kernel's sources as they were built (ties the figures to a tree)."""
     import hashlib
     hsh = hashlib.sha256()
@@ -181,7 +181,7 @@ def e2e(args):
     ref = None
     cu = centred(0.25)
     doc = {"tool": "tools/window_bench.py --e2e", "commit": args.commit,
-           "sources_sha256": sources_sha256(("window_band.hpp", "window.hip", "batch.cpp", "pipeline.cpp", "huff.hip", "huff_job.hpp")),
+           "sources_sha256": sources_sha256(("window_band.hpp", "window.hip", "batch.cpp", "batch_internal.hpp", "batch_layout.hpp", "batch_entropy.cpp", "pipeline.cpp", "huff.hip", "huff_job.hpp")),
            "library": os.path.basename(J._native.LIB_PATH), "host": socket.gethostname(), "device": device_identity(),
            "date": time.strftime("%Y-%m-%d %H:%M:%S"), "files": who,
            "workload": f"{W}x{H} 4:2:0 q85 files ({len(distinct)} distinct) through Pipeline.decode, device entropy decoding",
