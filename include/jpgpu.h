@@ -189,6 +189,43 @@ int jpgpu_batch_create_resized(int device, const jpgpu_image_desc *descs, const 
  * (xmin, n), `coefs` out_size x ksize int32 weights, zero beyond n; *ksize the row length.  With `bounds` and `coefs` NULL only
  * *ksize is set (to size the buffers).  in_size and out_size are 1..65535; anything else is JPGPU_ERR_FORMAT. */
 int jpgpu_resample_coefficients(uint32_t in_size, uint32_t out_size, int32_t *bounds, int32_t *coefs, uint32_t *ksize);
+/* ---- A tensor output: every image resampled, normalised and written channel-first, as the model reads it -----------------------
+ * jpgpu_batch_create_resized with a tensor format.  The output of image i is ncomp x out_h x out_w elements of `dtype`, planar (CHW)
+ * and packed:
+ *     elem(c, r, x) = T[c][ u8(r, flip_i ? out_w - 1 - x : x, c) ]
+ * u8 is the resized output of that image exactly as jpgpu_batch_create_resized defines it; flip_i is a flag per image
+ * (jpgpu_batch_set_flips; applied last, to the resampled image: a pure mirror of columns); T is a table of ncomp x 256 elements made
+ * on the host in IEEE single precision, one operation per statement:
+ *     a = (float)v / 255.0f;   b = a - mean[c];   t = b / std[c];
+ *     T[c][v] = t (f32), t rounded to nearest even to binary16 (f16), t rounded to nearest even to bfloat16 (bf16)
+ * — what torch's arange(256, uint8).to(float32).div(255).sub_(mean).div_(std) (then .to(dtype)) gives on the CPU, bit for bit.  The
+ * device looks the table up and does no float arithmetic: the result is exact by construction.  There is no resized u8 image in this
+ * mode: the resample's vertical pass writes the tensor (jpgpu_batch_path ends in "+resize+tensor").
+ *
+ * jpgpu_batch_out_bytes(i) is ncomp * out_h * out_w * sizeof(dtype); jpgpu_batch_out_offset / the output arena (the caller's with
+ * EXTERNAL_BUFFERS) / jpgpu_batch_download hold the tensor.  Image offsets are 256-byte aligned as everywhere: images whose tensor
+ * is a multiple of 256 bytes — 3 x 224 x 224 in any of the three dtypes — follow each other without a gap, so the arena of N such
+ * images IS one contiguous N x 3 x 224 x 224 tensor.
+ *
+ * Refusals: a std[c] that is 0 or not finite, or a mean[c] that is not finite, for c < ncomp of any image of the call, an unknown
+ * dtype, reserved != 0, a NULL format or an output size of 0: JPGPU_ERR_FORMAT; planar ColorTransform None images:
+ * JPGPU_ERR_UNSUPPORTED, as with an output size. */
+enum { JPGPU_TENSOR_F32 = 1, JPGPU_TENSOR_F16 = 2, JPGPU_TENSOR_BF16 = 3 };
+typedef struct jpgpu_tensor_format {
+    uint32_t dtype;    /* JPGPU_TENSOR_* */
+    uint32_t reserved; /* must be 0 */
+    float mean[4];
+    float std[4];
+} jpgpu_tensor_format;
+int jpgpu_batch_create_tensor(int device, const jpgpu_image_desc *descs, const jpgpu_window *windows, uint16_t out_w, uint16_t out_h,
+                              const jpgpu_tensor_format *format, uint32_t n_images, uint32_t flags, jpgpu_batch **out);
+/* The flip flag of every image (`flips`: n_images bytes, non-zero = mirrored; NULL: none) from the next jpgpu_batch_decode on: a
+ * field of the image's job record, sent with the job tables.  Never changes a size or an offset.  JPGPU_ERR_UNSUPPORTED on a batch
+ * without a tensor format. */
+int jpgpu_batch_set_flips(jpgpu_batch *b, const uint8_t *flips);
+/* The table T of a format for images of `nc` channels (1..4) as the batch computes it (pure host function, no device needed): `table`
+ * receives nc x 256 elements of the format's dtype (bf16 / f16 as their 16-bit patterns).  A refused format: JPGPU_ERR_FORMAT. */
+int jpgpu_tensor_table(const jpgpu_tensor_format *format, uint32_t nc, void *table);
 void jpgpu_batch_destroy(jpgpu_batch *b);
 const char *jpgpu_batch_last_error(const jpgpu_batch *b);
 

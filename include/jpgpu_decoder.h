@@ -229,6 +229,17 @@ int jpgpu_pipeline_set_scale(jpgpu_pipeline *p, uint16_t requested_width, uint16
  * changes nothing.  A change of the output size between calls creates the kept sub-batches anew; fresh windows at the same output
  * size are set in place. */
 int jpgpu_pipeline_set_output_size(jpgpu_pipeline *p, uint16_t width, uint16_t height);
+/* A tensor output for every image of the calls that follow (sticky, like the output size; NULL: off, the default — same routes,
+ * kernels, launches and bytes as ever): each image's result is the tensor of jpgpu_batch_create_tensor (jpgpu.h) — ncomp x height x
+ * width elements of format->dtype, channel-first, normalised with the format's means and stds — at the output size in force.  The
+ * dtype and `reserved` are checked here (JPGPU_ERR_FORMAT, nothing changed); that an output size is set is checked at the next decode,
+ * which fails as a whole with JPGPU_ERR_FORMAT before anything is decoded when there is none; the means and stds are checked against
+ * every image's own channels (a std that is 0 or not finite, a mean that is not finite: that image fails alone with
+ * JPGPU_ERR_FORMAT).  jpgpu_pipeline_pixel_bytes / _pixels_device /
+ * _pixels_host / _download, the pinned download block, the JPGPU_PIPELINE_GATHER copies and timings.pixel_bytes hold / count the
+ * tensor's bytes; timings.images_resized counts the images.  A change of the format between calls creates the kept sub-batches anew,
+ * as a changed output size does. */
+int jpgpu_pipeline_set_tensor_output(jpgpu_pipeline *p, const jpgpu_tensor_format *format);
 /* Decoder::set_color_transform (src/decoder.rs:158-161) for every image of the calls that follow: one of the JPGPU_CT_* values of
  * jpgpu.h instead of what determine_color_transform finds per image; a negative value: per image again (the default). */
 int jpgpu_pipeline_set_color_transform(jpgpu_pipeline *p, int color_transform);
@@ -254,6 +265,13 @@ int jpgpu_pipeline_decode(jpgpu_pipeline *p, const uint8_t *const *data, const s
  * place an image whose new window covers its whole output stays with the window kernel: same bytes; timings.images_windowed counts it.) */
 int jpgpu_pipeline_decode_windowed(jpgpu_pipeline *p, const uint8_t *const *data, const size_t *len, const jpgpu_window *windows,
                                    uint32_t n_images, uint32_t flags);
+/* jpgpu_pipeline_decode_windowed with a flip flag per image (`flips`: n_images bytes, non-zero = the image's columns mirrored, applied
+ * last, to the resampled image; NULL: exactly jpgpu_pipeline_decode_windowed).  Flips need a tensor output
+ * (jpgpu_pipeline_set_tensor_output): without one the call fails with JPGPU_ERR_FORMAT before anything is decoded.  Other flips for
+ * the same images — with or without other windows, a loader's fresh augmentation — never create a kept sub-batch anew: the flips
+ * are set in place (jpgpu_batch_set_flips), the windows as jpgpu_pipeline_decode_windowed sets them. */
+int jpgpu_pipeline_decode_augmented(jpgpu_pipeline *p, const uint8_t *const *data, const size_t *len, const jpgpu_window *windows,
+                                    const uint8_t *flips, uint32_t n_images, uint32_t flags);
 /* The window image i of the last call was decoded with: what the caller passed, or 0, 0, W, H of the output grid when it had none
  * (JPGPU_ERR_FORMAT for an image without a frame or whose window was refused). */
 int jpgpu_pipeline_image_window(const jpgpu_pipeline *p, uint32_t image, jpgpu_window *out);

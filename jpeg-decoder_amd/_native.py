@@ -70,6 +70,14 @@ class Window(C.Structure):
     _fields_ = [("x", C.c_uint16), ("y", C.c_uint16), ("w", C.c_uint16), ("h", C.c_uint16)]
 
 
+TENSOR_F32, TENSOR_F16, TENSOR_BF16 = 1, 2, 3
+
+
+class TensorFormatStruct(C.Structure):
+    """jpgpu_tensor_format: dtype (TENSOR_*), reserved = 0, mean[4], std[4]."""
+    _fields_ = [("dtype", C.c_uint32), ("reserved", C.c_uint32), ("mean", C.c_float * 4), ("std", C.c_float * 4)]
+
+
 class PipelineTimings(C.Structure):
     _fields_ = [(n, C.c_double) for n in ("headers_ms", "setup_ms", "entropy_and_upload_ms", "kernels_ms", "download_ms", "total_ms")] + \
                [("threads", C.c_uint32), ("images_ok", C.c_uint32), ("jpeg_bytes", C.c_uint64), ("coefficient_bytes", C.c_uint64),
@@ -125,6 +133,10 @@ _PROTOS = {
     "jpgpu_batch_create_windowed": (C.c_int, [C.c_int, C.POINTER(ImageDesc), C.POINTER(Window), C.c_uint32, C.c_uint32, C.POINTER(C.c_void_p)]),
     "jpgpu_batch_create_resized": (C.c_int, [C.c_int, C.POINTER(ImageDesc), C.POINTER(Window), C.c_uint16, C.c_uint16, C.c_uint32, C.c_uint32,
                                              C.POINTER(C.c_void_p)]),
+    "jpgpu_batch_create_tensor": (C.c_int, [C.c_int, C.POINTER(ImageDesc), C.POINTER(Window), C.c_uint16, C.c_uint16, C.POINTER(TensorFormatStruct), C.c_uint32,
+                                            C.c_uint32, C.POINTER(C.c_void_p)]),
+    "jpgpu_batch_set_flips": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "jpgpu_tensor_table": (C.c_int, [C.POINTER(TensorFormatStruct), C.c_uint32, C.c_void_p]),
     "jpgpu_resample_coefficients": (C.c_int, [C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.POINTER(C.c_uint32)]),
     "jpgpu_batch_destroy": (None, [C.c_void_p]),
     "jpgpu_batch_last_error": (C.c_char_p, [C.c_void_p]),
@@ -183,6 +195,7 @@ _PROTOS = {
     "jpgpu_trim_caches": (None, []),
     "jpgpu_pipeline_decode": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), C.c_uint32, C.c_uint32]),
     "jpgpu_pipeline_decode_windowed": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), C.POINTER(Window), C.c_uint32, C.c_uint32]),
+    "jpgpu_pipeline_decode_augmented": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), C.POINTER(Window), C.c_void_p, C.c_uint32, C.c_uint32]),
     "jpgpu_pipeline_image_window": (C.c_int, [C.c_void_p, C.c_uint32, C.POINTER(Window)]),
     "jpgpu_pipeline_image_status": (C.c_int, [C.c_void_p, C.c_uint32]),
     "jpgpu_pipeline_image_error": (C.c_char_p, [C.c_void_p, C.c_uint32]),
@@ -193,6 +206,7 @@ _PROTOS = {
     "jpgpu_pipeline_kernel_path": (C.c_char_p, [C.c_void_p]),
     "jpgpu_pipeline_set_scale": (C.c_int, [C.c_void_p, C.c_uint16, C.c_uint16]),
     "jpgpu_pipeline_set_output_size": (C.c_int, [C.c_void_p, C.c_uint16, C.c_uint16]),
+    "jpgpu_pipeline_set_tensor_output": (C.c_int, [C.c_void_p, C.POINTER(TensorFormatStruct)]),
     "jpgpu_pipeline_set_color_transform": (C.c_int, [C.c_void_p, C.c_int]),
     "jpgpu_pipeline_set_max_decoding_buffer_size": (C.c_int, [C.c_void_p, C.c_size_t]),
     "jpgpu_pipeline_download": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]),

@@ -47,6 +47,62 @@ def output_size_pair(output_size):
     return w, h
 
 
+class TensorFormat:
+    """The tensor a decode writes instead of resized bytes (jpgpu_tensor_format): ``dtype`` "float32", "float16" or "bfloat16",
+    ``mean`` and ``std`` per channel (up to four; missing channels: mean 0, std 1).  Element (c, r, x) of an image is
+    ``T[c][u8[r, x, c]]`` with ``T[c][v] = (v / 255 - mean[c]) / std[c]`` computed in float32, one operation after the other, then rounded
+    once to the dtype: what ``torch.from_numpy(u8).permute(2, 0, 1).to(float32).div(255).sub(mean).div(std).to(dtype)``
+    gives, bit for bit."""
+    DTYPES = {"float32": (N.TENSOR_F32, np.float32), "float16": (N.TENSOR_F16, np.float16), "bfloat16": (N.TENSOR_BF16, np.uint16)}
+
+    def __init__(self, dtype="float32", mean=(0.0, 0.0, 0.0, 0.0), std=(1.0, 1.0, 1.0, 1.0)):
+        dtype = str(dtype).replace("torch.", "")
+        if dtype not in self.DTYPES:
+            raise ValueError(f"tensor dtype {dtype!r}: one of {sorted(self.DTYPES)}")
+        mean, std = [float(v) for v in mean], [float(v) for v in std]
+        if len(mean) > 4 or len(std) > 4:
+            raise ValueError("at most four means / stds")
+        self.dtype = dtype
+        self.mean = tuple(mean + [0.0] * (4 - len(mean)))
+        self.std = tuple(std + [1.0] * (4 - len(std)))
+
+    @property
+    def numpy_dtype(self):
+        """The dtype of the arrays returned: np.float32, np.float16, and np.uint16 bit patterns for bfloat16 (numpy has no such type)."""
+        return self.DTYPES[self.dtype][1]
+
+    @property
+    def itemsize(self):
+        return np.dtype(self.numpy_dtype).itemsize
+
+    def struct(self):
+        s = N.TensorFormatStruct()
+        s.dtype, s.reserved = self.DTYPES[self.dtype][0], 0
+        for c in range(4):
+            s.mean[c], s.std[c] = self.mean[c], self.std[c]
+        return s
+
+    def table(self, nc):
+        """jpgpu_tensor_table: the (nc, 256) lookup table as the library computes it."""
+        out = np.zeros((nc, 256), self.numpy_dtype)
+        s = self.struct()
+        check(N.lib().jpgpu_tensor_table(C.byref(s), nc, out.ctypes.data), b"jpgpu_tensor_table: refused format")
+        return out
+
+    def __repr__(self):
+        return f"TensorFormat({self.dtype!r}, mean={self.mean}, std={self.std})"
+
+
+def flip_bytes(flips, n):
+    """`flips`: None or one truth value per image -> (ctypes array of n bytes or None)."""
+    if flips is None:
+        return None
+    flips = [1 if f else 0 for f in flips]
+    if len(flips) != n:
+        raise ValueError(f"{len(flips)} flips for {n} images")
+    return (C.c_uint8 * max(n, 1))(*flips)
+
+
 class Batch:
     """N independent images decoded per launch (jpgpu_batch_*).
 
@@ -62,14 +118,25 @@ class Batch:
     with antialiasing (Pillow's ``Image.resize((w, h), BILINEAR)`` arithmetic, crop first, horizontal pass first)
     of what it gives without: its window, or its whole output.  out_bytes / out_offset / download / the output arena hold h * w * nc
     bytes per image, interleaved; `path` ends in "+resize".  Planar output (ColorTransform None, more than one component) is refused
-    (UnsupportedError), a size of 0 or above 2048 is a FormatError."""
+    (UnsupportedError), a size of 0 or above 2048 is a FormatError.
 
-    def __init__(self, descs, device=0, flags=N.BATCH_DEFAULT, windows=None, output_size=None):
+    tensor: None or a TensorFormat (jpgpu_batch_create_tensor; needs an output_size, else FormatError).  Every image's output is then
+    its resized pixels normalised and channel-first: nc x h x w elements of the format's dtype, written by the resample itself;
+    out_bytes / out_offset / the output arena hold them, ``download(i)`` returns an array of shape (nc, h, w) (np.uint16 bit patterns
+    for bfloat16), `path` ends in "+resize+tensor".  ``set_flips([...])`` mirrors images' columns from the next decode on.  Images of
+    3 x 224 x 224 follow each other without a gap: a ``torch.empty(N, 3, 224, 224)`` bound with BATCH_EXTERNAL_BUFFERS is the result."""
+
+    def __init__(self, descs, device=0, flags=N.BATCH_DEFAULT, windows=None, output_size=None, tensor=None):
         self._h = C.c_void_p()
         arr = (N.ImageDesc * len(descs))(*descs)
         wins = window_structs(windows, len(descs))
         self.output_size = None if output_size is None else output_size_pair(output_size)
-        if self.output_size is not None:
+        self.tensor = tensor
+        if tensor is not None:
+            w, h = self.output_size if self.output_size is not None else (0, 0)
+            fmt = tensor.struct()
+            st = N.lib().jpgpu_batch_create_tensor(device, arr, wins, w, h, C.byref(fmt), len(descs), flags, C.byref(self._h))
+        elif self.output_size is not None:
             st = N.lib().jpgpu_batch_create_resized(device, arr, wins, self.output_size[0], self.output_size[1], len(descs), flags, C.byref(self._h))
         elif wins is None:
             st = N.lib().jpgpu_batch_create(device, arr, len(descs), flags, C.byref(self._h))
@@ -179,11 +246,20 @@ class Batch:
     def synchronize(self, stream=None):
         self._check(N.lib().jpgpu_batch_synchronize(self._h, stream))
 
+    def set_flips(self, flips):
+        """jpgpu_batch_set_flips: one truth value per image (None: no image flipped), in force from the next decode on.  A batch
+        without `tensor` raises UnsupportedError."""
+        arr = flip_bytes(flips, self.n_images)
+        self._check(N.lib().jpgpu_batch_set_flips(self._h, arr))
+
     def download(self, image):
         n = self.out_bytes(image)
         out = np.empty(max(n, 1), dtype=np.uint8)
         got = C.c_size_t(0)
         self._check(N.lib().jpgpu_batch_download(self._h, image, out.ctypes.data, out.size, C.byref(got)))
+        if self.tensor is not None:
+            w, h = self.output_size
+            return out[: got.value].view(self.tensor.numpy_dtype).reshape(-1, h, w)
         return out[: got.value]
 
     def time(self, iters, stream=None):

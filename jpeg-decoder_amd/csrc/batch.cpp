@@ -68,10 +68,35 @@ static int batch_upload_qt(jpgpu_batch *b) {
     return JPGPU_OK;
 }
 
+// The TensorJobs of a tensor batch: every image's resample job, its plane pitch and its flip.  They travel on the decode's stream from a
+// pinned mirror (fresh flips come with every call of a loader: a blocking copy per sub-batch would hold the uploader thread up).
+static int batch_upload_tensor_jobs(jpgpu_batch *b, hipStream_t stream) {
+    const uint32_t n = (uint32_t)b->descs.size();
+    if (!b->h_tn_jobs) {
+        B_HIP(hipHostMalloc((void **)&b->h_tn_jobs, (size_t)n * sizeof(TensorJob), hipHostMallocDefault));
+        B_HIP(hipEventCreateWithFlags(&b->tn_sent, hipEventDisableTiming));
+    } else {
+        B_HIP(hipEventSynchronize(b->tn_sent));  // (the copy before this one has read the mirror)
+    }
+    for (uint32_t i = 0; i < n; i++) {
+        b->h_tn_jobs[i].r = b->rs_jobs[i];
+        b->h_tn_jobs[i].plane = b->rs_w * b->rs_h;
+        b->h_tn_jobs[i].flip = b->tn_flips[i] ? 1u : 0u;
+    }
+    B_HIP(hipMemcpyAsync(b->d_tn_jobs, b->h_tn_jobs, (size_t)n * sizeof(TensorJob), hipMemcpyHostToDevice, stream));
+    B_HIP(hipEventRecord(b->tn_sent, stream));
+    b->tn_dirty = false;
+    return JPGPU_OK;
+}
+
 static int batch_refresh_jobs(jpgpu_batch *b, hipStream_t stream = nullptr) {
     // host-side classes are part of the launch tables (one launch per class: fused_bind); with device-side classes they
     // travel in a small table of their own, asynchronously, and the launch tables stay as they are
     const bool need_bind = b->jobs_dirty || (b->cls_dirty && !b->dev_classes);
+    if (!need_bind && b->tn_dirty && b->d_coef && b->d_out) {  // (other flips alone: the TensorJobs, nothing else)
+        int rc = batch_upload_tensor_jobs(b, stream);
+        if (rc) return rc;
+    }
     if (!need_bind && !b->cls_dirty) return JPGPU_OK;
     if (!b->d_coef || !b->d_out) return set_err(b->err, JPGPU_ERR_FORMAT, "batch has no device buffers bound");
     uint8_t *const pix = pix_base(b);
@@ -126,7 +151,12 @@ static int batch_refresh_jobs(jpgpu_batch *b, hipStream_t stream = nullptr) {
     }
     if (b->rs_w) {
         for (uint32_t i = 0; i < n; i++) b->rs_jobs[i].src = pix + pix_off[i], b->rs_jobs[i].dst = b->d_out + b->out_off[i];
-        B_HIP(hipMemcpy(b->d_rs_jobs, b->rs_jobs.data(), (size_t)n * sizeof(ResampleJob), hipMemcpyHostToDevice));
+        if (b->tn_es) {
+            rc = batch_upload_tensor_jobs(b, stream);
+            if (rc) return rc;
+        } else {
+            B_HIP(hipMemcpy(b->d_rs_jobs, b->rs_jobs.data(), (size_t)n * sizeof(ResampleJob), hipMemcpyHostToDevice));
+        }
     }
     if (b->qt_dirty) {
         rc = batch_upload_qt(b);
@@ -139,9 +169,9 @@ static int batch_refresh_jobs(jpgpu_batch *b, hipStream_t stream = nullptr) {
 
 extern "C" {
 
-// rs_w, rs_h: the output size of jpgpu_batch_create_resized (0, 0: none)
-static int batch_create(int device, const jpgpu_image_desc *descs, const jpgpu_window *windows, uint32_t rs_w, uint32_t rs_h, uint32_t n_images,
-                        uint32_t flags, jpgpu_batch **out) {
+// rs_w, rs_h: the output size of jpgpu_batch_create_resized (0, 0: none); tensor: the format of jpgpu_batch_create_tensor (NULL: none)
+static int batch_create(int device, const jpgpu_image_desc *descs, const jpgpu_window *windows, uint32_t rs_w, uint32_t rs_h,
+                        const jpgpu_tensor_format *tensor, uint32_t n_images, uint32_t flags, jpgpu_batch **out) {
     if (!out) return JPGPU_ERR_FORMAT;
     *out = nullptr;
     if (!descs || n_images == 0 || n_images > 65535) return JPGPU_ERR_FORMAT;
@@ -152,6 +182,13 @@ static int batch_create(int device, const jpgpu_image_desc *descs, const jpgpu_w
     const bool resized = rs_w != 0 || rs_h != 0;
     if (resized && (rs_w == 0 || rs_h == 0 || rs_w > RS_MAX_OUT || rs_h > RS_MAX_OUT))
         return set_err(b->err, JPGPU_ERR_FORMAT, "output size %ux%u: width and height must be 1..%u", rs_w, rs_h, RS_MAX_OUT);
+    if (tensor) {  // (the format against the channels of every image of the call, before anything is allocated)
+        if (!resized) return set_err(b->err, JPGPU_ERR_FORMAT, "a tensor format needs an output size");
+        uint32_t nc_max = 1;
+        for (uint32_t i = 0; i < n_images; i++) nc_max = std::max(nc_max, std::min<uint32_t>(descs[i].ncomp, 4u));
+        const char *why = nullptr;
+        if (!tensor_format_ok(tensor->dtype, tensor->reserved, tensor->mean, tensor->std, nc_max, why)) return set_err(b->err, JPGPU_ERR_FORMAT, "tensor format: %s", why);
+    }
     int rc = use_device(device, b->err);
     if (rc) return rc;
     b->descs.assign(descs, descs + n_images);
@@ -231,7 +268,8 @@ static int batch_create(int device, const jpgpu_image_desc *descs, const jpgpu_w
     if (resized) {  // what was laid out so far is the intermediate arena; the output arena holds rs_h x rs_w x ncomp bytes per image
         b->rs_w = rs_w, b->rs_h = rs_h;
         b->pix_off = b->out_off, b->pix_len = b->out_len, b->pix_bytes = b->out_bytes;
-        for (uint32_t i = 0; i < n_images; i++) lens[i] = (size_t)rs_w * rs_h * b->descs[i].ncomp;
+        if (tensor) b->tn_es = tensor_elem_bytes(tensor->dtype), b->tn_flips.assign(n_images, 0);
+        for (uint32_t i = 0; i < n_images; i++) lens[i] = (size_t)rs_w * rs_h * b->descs[i].ncomp * (tensor ? b->tn_es : 1u);
         b->out_bytes = arena_layout(lens, b->out_off, b->out_len);
     }
 
@@ -260,6 +298,7 @@ static int batch_create(int device, const jpgpu_image_desc *descs, const jpgpu_w
     if (!b->win.empty()) b->path = b->path.empty() ? "window" : "mixed";
     if (b->path.empty()) b->path = "generic";
     if (resized) b->path += "+resize";
+    if (tensor) b->path += "+tensor";
     const size_t full = arena_layout(b->out_full_len);  // (what the whole images take)
     if (!(flags & JPGPU_BATCH_EXTERNAL_BUFFERS)) {
         B_HIP(hipMalloc((void **)&b->d_coef, b->coef_bytes));
@@ -272,7 +311,17 @@ static int batch_create(int device, const jpgpu_image_desc *descs, const jpgpu_w
     if (resized) {  // (the same headroom for other windows, in the intermediate arena)
         b->pix_cap = b->win.empty() ? b->pix_bytes : arena_headroom(b->pix_bytes, full);
         B_HIP(hipMalloc((void **)&b->d_pix, b->pix_cap));
-        B_HIP(hipMalloc((void **)&b->d_rs_jobs, (size_t)n_images * sizeof(ResampleJob)));
+        if (tensor) {  // (the table of four channels: every image looks up its own first ncomp rows)
+            B_HIP(hipMalloc((void **)&b->d_tn_jobs, (size_t)n_images * sizeof(TensorJob)));
+            B_HIP(hipMalloc(&b->d_tn_table, TN_TABLE_MAX));
+            std::vector<uint32_t> table(TN_TABLE_MAX / 4u, 0u);
+            uint32_t nc_max = 1;
+            for (uint32_t i = 0; i < n_images; i++) nc_max = std::max<uint32_t>(nc_max, b->descs[i].ncomp);
+            tensor_table(tensor->dtype, tensor->mean, tensor->std, nc_max, table.data());
+            B_HIP(hipMemcpy(b->d_tn_table, table.data(), TN_TABLE_MAX, hipMemcpyHostToDevice));
+        } else {
+            B_HIP(hipMalloc((void **)&b->d_rs_jobs, (size_t)n_images * sizeof(ResampleJob)));
+        }
     }
     if (!b->generic_ids.empty()) B_HIP(hipMalloc((void **)&b->d_planes, b->plane_bytes_total));
     for (FusedPlan &fp : b->fused) {
@@ -293,11 +342,11 @@ static int batch_create(int device, const jpgpu_image_desc *descs, const jpgpu_w
 }
 
 int jpgpu_batch_create(int device, const jpgpu_image_desc *descs, uint32_t n_images, uint32_t flags, jpgpu_batch **out) {
-    return batch_create(device, descs, nullptr, 0, 0, n_images, flags, out);
+    return batch_create(device, descs, nullptr, 0, 0, nullptr, n_images, flags, out);
 }
 int jpgpu_batch_create_windowed(int device, const jpgpu_image_desc *descs, const jpgpu_window *windows, uint32_t n_images, uint32_t flags,
                                 jpgpu_batch **out) {
-    return batch_create(device, descs, windows, 0, 0, n_images, flags, out);
+    return batch_create(device, descs, windows, 0, 0, nullptr, n_images, flags, out);
 }
 int jpgpu_batch_create_resized(int device, const jpgpu_image_desc *descs, const jpgpu_window *windows, uint16_t out_w, uint16_t out_h,
                                uint32_t n_images, uint32_t flags, jpgpu_batch **out) {
@@ -307,7 +356,25 @@ int jpgpu_batch_create_resized(int device, const jpgpu_image_desc *descs, const 
         *out = b;
         return set_err(b->err, JPGPU_ERR_FORMAT, "output size %ux%u: width and height must be 1..%u", out_w, out_h, RS_MAX_OUT);
     }
-    return batch_create(device, descs, windows, out_w, out_h, n_images, flags, out);
+    return batch_create(device, descs, windows, out_w, out_h, nullptr, n_images, flags, out);
+}
+int jpgpu_batch_create_tensor(int device, const jpgpu_image_desc *descs, const jpgpu_window *windows, uint16_t out_w, uint16_t out_h,
+                              const jpgpu_tensor_format *format, uint32_t n_images, uint32_t flags, jpgpu_batch **out) {
+    if (out_w == 0 || out_h == 0 || !format) {  // (no output size, no format: refused here — below they would mean "none")
+        if (!out) return JPGPU_ERR_FORMAT;
+        jpgpu_batch *b = new jpgpu_batch();
+        *out = b;
+        if (!format) return set_err(b->err, JPGPU_ERR_FORMAT, "jpgpu_batch_create_tensor: no tensor format");
+        return set_err(b->err, JPGPU_ERR_FORMAT, "a tensor format needs an output size (%ux%u: width and height must be 1..%u)", out_w, out_h, RS_MAX_OUT);
+    }
+    return batch_create(device, descs, windows, out_w, out_h, format, n_images, flags, out);
+}
+int jpgpu_batch_set_flips(jpgpu_batch *b, const uint8_t *flips) {
+    if (!b) return JPGPU_ERR_FORMAT;
+    if (!b->tn_es) return set_err(b->err, JPGPU_ERR_UNSUPPORTED, "jpgpu_batch_set_flips: the batch has no tensor format");
+    for (size_t i = 0; i < b->tn_flips.size(); i++) b->tn_flips[i] = flips && flips[i] ? 1 : 0;
+    b->tn_dirty = true;
+    return JPGPU_OK;
 }
 
 void jpgpu_batch_destroy(jpgpu_batch *b) {
@@ -320,6 +387,10 @@ void jpgpu_batch_destroy(jpgpu_batch *b) {
         if (b->d_planes) hipFree(b->d_planes);
         if (b->d_pix) hipFree(b->d_pix);
         if (b->d_rs_jobs) hipFree(b->d_rs_jobs);
+        if (b->d_tn_jobs) hipFree(b->d_tn_jobs);
+        if (b->d_tn_table) hipFree(b->d_tn_table);
+        if (b->h_tn_jobs) hipHostFree(b->h_tn_jobs);
+        if (b->tn_sent) hipEventDestroy(b->tn_sent);
         if (b->d_rs_tab) hipFree(b->d_rs_tab);
         if (b->d_qt) hipFree(b->d_qt);
         if (b->d_compact) hipFree(b->d_compact);
@@ -762,7 +833,10 @@ int jpgpu_batch_decode(jpgpu_batch *b, void *hip_stream) {
     if (!b->win.empty())  // (windows: after the others)
         B_HIP(launch_window_band(b->win.d_geoms, b->win.d_image_jobs, b->win.d_plane_jobs, (uint32_t)b->win.ids.size(), b->win.max_tiles_x, b->win.max_bands,
                                  b->win.lds_bytes, b->win.scales, s));
-    if (b->rs_w)  // (an output size: every image's pixels, wherever the launches above left them in the intermediate arena)
+    if (b->tn_es && b->tn_sent) B_HIP(hipStreamWaitEvent(s, b->tn_sent, 0));  // (the jobs may have gone up on another stream than this one)
+    if (b->tn_es)  // (a tensor output: the same resample, its vertical pass writes every image's tensor)
+        B_HIP(launch_resample_tensor(b->d_tn_jobs, b->d_rs_tab, b->d_tn_table, b->tn_es, (uint32_t)b->descs.size(), b->rs_max_bands, b->rs_lds_bytes, s));
+    else if (b->rs_w)  // (an output size: every image's pixels, wherever the launches above left them in the intermediate arena)
         B_HIP(launch_resample_band(b->d_rs_jobs, b->d_rs_tab, (uint32_t)b->descs.size(), b->rs_max_bands, b->rs_lds_bytes, s));
     if (b->phase_events_valid) B_HIP(hipEventRecord(b->ev_phase[5], s));
     return JPGPU_OK;

@@ -20,6 +20,7 @@
 #include "kernels.hpp"
 #include "range_stats.hpp"
 #include "resample_band.hpp"
+#include "tensor_band.hpp"
 #include "window_band.hpp"
 
 using namespace jpgpu;
@@ -130,6 +131,16 @@ struct jpgpu_batch {
     int32_t *d_rs_tab = nullptr;
     size_t rs_tab_cap = 0;             // int32 words behind d_rs_tab
     uint32_t rs_max_bands = 0, rs_lds_bytes = 0;
+    // A tensor output (jpgpu_batch_create_tensor, tensor_band.hpp; tn_es == 0: none): an output size whose resample launch writes the
+    // normalised CHW tensor of every image instead of its resized pixels.  The output arena holds ncomp x rs_h x rs_w elements per image;
+    // the planner, the tables and rs_jobs are the output size's, the device jobs are TensorJobs (rs_jobs[i] + the image's flip).
+    uint32_t tn_es = 0;                // bytes per element
+    std::vector<uint8_t> tn_flips;     // per image (jpgpu_batch_set_flips)
+    bool tn_dirty = false;             // the flips changed: the TensorJobs go up before the next decode
+    TensorJob *d_tn_jobs = nullptr;
+    TensorJob *h_tn_jobs = nullptr;    // pinned mirror the jobs travel from, on the decode's stream
+    hipEvent_t tn_sent = nullptr;      // behind the last copy out of the mirror
+    void *d_tn_table = nullptr;        // 4 x 256 elements
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
     // compact transport (compact.hpp): staging area in HBM, allocated at the first jpgpu_batch_upload_compact
     std::mutex compact_mutex;

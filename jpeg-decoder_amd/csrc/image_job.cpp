@@ -11,6 +11,7 @@
 
 #include "compact.hpp"
 #include "resample_band.hpp"
+#include "tensor_band.hpp"
 
 namespace jpgpu {
 
@@ -191,6 +192,14 @@ int jpgpu_resample_coefficients(uint32_t in_size, uint32_t out_size, int32_t *bo
     if (in_size == 0 || out_size == 0 || in_size > 65535u || out_size > 65535u || !ksize || (!bounds) != (!coefs)) return JPGPU_ERR_FORMAT;
     *ksize = jpgpu::resample_ksize(in_size, out_size);
     if (bounds) jpgpu::resample_coefficients(in_size, out_size, bounds, coefs, *ksize);
+    return JPGPU_OK;
+}
+
+// the table of a tensor format (tensor_band.hpp; the batch fills its own with the same function)
+int jpgpu_tensor_table(const jpgpu_tensor_format *format, uint32_t nc, void *table) {
+    const char *why = nullptr;
+    if (!format || !table || !jpgpu::tensor_format_ok(format->dtype, format->reserved, format->mean, format->std, nc, why)) return JPGPU_ERR_FORMAT;
+    jpgpu::tensor_table(format->dtype, format->mean, format->std, nc, table);
     return JPGPU_OK;
 }
 

@@ -24,6 +24,7 @@
 #include "compact.hpp"
 #include "host/frontend.hpp"
 #include "host_common.hpp"
+#include "tensor_band.hpp"
 
 using jpgpu::host::DecodeError;
 using jpgpu::host::Frontend;
@@ -257,6 +258,9 @@ struct SubBatch {
     std::vector<size_t> stage_off;    // compact mode: [image*4 + comp] offset of the component's region in h_coef
     std::vector<jpgpu_window> wins;   // the window of every image as the batch was created with it (w == 0: none); empty: no image has one
     uint16_t rs_w = 0, rs_h = 0;      // the output size the batch was created with (jpgpu_pipeline_set_output_size; 0 x 0: none)
+    bool tensor = false;              // the tensor format the batch was created with (jpgpu_pipeline_set_tensor_output), if any
+    jpgpu_tensor_format tn{};
+    std::vector<uint8_t> flips;       // a tensor batch: the flip of every image as the batch holds it (jpgpu_batch_set_flips)
     uint32_t remaining = 0;  // images not yet uploaded / failed (uploader thread only)
     hipEvent_t ready[kCopyStreams] = {nullptr, nullptr, nullptr, nullptr};
     hipEvent_t decoded = nullptr;  // recorded on the compute stream behind the sub-batch's pixel kernels: downloads and the gather wait for it
@@ -271,6 +275,8 @@ struct SubBatch {
         stage_off.clear();
         wins.clear();
         rs_w = rs_h = 0;
+        tensor = false;
+        flips.clear();
     }
 };
 
@@ -311,6 +317,8 @@ struct jpgpu_pipeline {
     hipStream_t d2h[kD2HStreams] = {};
     uint16_t req_w = 0, req_h = 0;  // jpgpu_pipeline_set_scale (0 x 0: full size)
     uint16_t rs_w = 0, rs_h = 0;    // jpgpu_pipeline_set_output_size (0 x 0: none)
+    bool tensor = false;            // jpgpu_pipeline_set_tensor_output
+    jpgpu_tensor_format tn{};
     int color_transform = -1;       // jpgpu_pipeline_set_color_transform (< 0: what every image says itself)
     size_t max_bytes = SIZE_MAX;    // jpgpu_pipeline_set_max_decoding_buffer_size
     uint32_t n_compute = kComputeStreamsDefault;  // streams in use (JPGPU_PIPE_STREAMS: tuning knob, up to kComputeStreams)
@@ -343,7 +351,8 @@ static const jpgpu_pipeline *child_of(const jpgpu_pipeline *p, uint32_t &image) 
     image /= n;
     return c;
 }
-static int multi_decode(jpgpu_pipeline *p, const uint8_t *const *data, const size_t *len, const jpgpu_window *windows, uint32_t n, uint32_t flags);
+static int multi_decode(jpgpu_pipeline *p, const uint8_t *const *data, const size_t *len, const jpgpu_window *windows, const uint8_t *flips, uint32_t n,
+                        uint32_t flags);
 // Up to how many scans does a call walk its progressive frames a WAVE per scan (pipelined, huff_prog_job.hpp)?  Always: the launch
 // order keeps a frame's waves on one XCD, producers in front (csrc/batch_entropy.cpp), so an oversubscribed launch cannot starve a producer
 // (round 5's lanes had to fit the device at once).  Beyond the limit: a wave per TRACK, its scans one after the other —
@@ -616,13 +625,21 @@ int jpgpu_pipeline_decode(jpgpu_pipeline *p, const uint8_t *const *data, const s
 
 int jpgpu_pipeline_decode_windowed(jpgpu_pipeline *p, const uint8_t *const *data, const size_t *len, const jpgpu_window *windows, uint32_t n,
                                    uint32_t flags) {
+    return jpgpu_pipeline_decode_augmented(p, data, len, windows, nullptr, n, flags);
+}
+
+int jpgpu_pipeline_decode_augmented(jpgpu_pipeline *p, const uint8_t *const *data, const size_t *len, const jpgpu_window *windows, const uint8_t *flips,
+                                    uint32_t n, uint32_t flags) {
     jpgpu::TraceRange roctx_range("jpgpu_pipeline_decode");
     // (unknown bits are refused, not ignored: 8u was round 2-3's JPGPU_PIPELINE_PROGRESSIVE_DELTAS, removed in round 4 — a caller built
     // against that header would otherwise silently get another transport: ADVICE r4)
     constexpr uint32_t kKnownFlags = JPGPU_PIPELINE_DOWNLOAD | JPGPU_PIPELINE_DENSE | JPGPU_PIPELINE_DEVICE_ENTROPY | JPGPU_PIPELINE_GATHER |
                                      JPGPU_PIPELINE_HOST_LIGHT | JPGPU_PIPELINE_HOST_STAGED | JPGPU_PIPELINE_INPUT_PINNED | JPGPU_PIPELINE_PROGRESSIVE_ON_HOST;
     if (p && (flags & ~kKnownFlags)) return jpgpu::set_err(p->err, JPGPU_ERR_FORMAT, "jpgpu_pipeline_decode: unknown flag bits 0x%x (this library: %s)", flags & ~kKnownFlags, jpgpu_version());
-    if (p && !p->children.empty()) return (n && (!data || !len)) ? JPGPU_ERR_FORMAT : multi_decode(p, data, len, windows, n, flags);
+    // (a tensor output needs an output size, flips a tensor output: refused before anything is decoded)
+    if (p && p->tensor && !p->rs_w) return jpgpu::set_err(p->err, JPGPU_ERR_FORMAT, "jpgpu_pipeline_decode: a tensor output needs an output size (jpgpu_pipeline_set_output_size)");
+    if (p && flips && !p->tensor) return jpgpu::set_err(p->err, JPGPU_ERR_FORMAT, "jpgpu_pipeline_decode_augmented: flips need a tensor output (jpgpu_pipeline_set_tensor_output)");
+    if (p && !p->children.empty()) return (n && (!data || !len)) ? JPGPU_ERR_FORMAT : multi_decode(p, data, len, windows, flips, n, flags);
     if (!p || !p->pool || (n && (!data || !len))) return JPGPU_ERR_FORMAT;
     if ((flags & JPGPU_PIPELINE_GATHER) && !p->gather_on) flags &= ~(uint32_t)JPGPU_PIPELINE_GATHER;  // (one device: the pixels are where a gather would put them)
     int rc = jpgpu::use_device(p->device, p->err);
@@ -727,6 +744,9 @@ int jpgpu_pipeline_decode_windowed(jpgpu_pipeline *p, const uint8_t *const *data
                 // (an output size: planar output has no resample — the image fails alone, like a refused window)
                 if (p->rs_w && planar)
                     throw DecodeError{JPGPU_ERR_UNSUPPORTED, "no output size for planar output (ColorTransform None with more than one component)"};
+                const char *bad = nullptr;  // (the format's means and stds against THIS image's channels)
+                if (p->tensor && !jpgpu::tensor_format_ok(p->tn.dtype, p->tn.reserved, p->tn.mean, p->tn.std, d.ncomp, bad))
+                    throw DecodeError{JPGPU_ERR_FORMAT, std::string("tensor format: ") + bad};
             }
             if (device_entropy && p->infos[i].coding_process == JPGPU_CODING_DCT_PROGRESSIVE) {
                 // a progressive frame: its scans as tracks for the device (huff_prog_wave.hpp), if the stream is plainly eligible;
@@ -827,6 +847,7 @@ int jpgpu_pipeline_decode_windowed(jpgpu_pipeline *p, const uint8_t *const *data
         const uint32_t first = bounds[j], last = bounds[j + 1];
         std::vector<jpgpu_image_desc> descs;
         std::vector<jpgpu_window> wins;  // (stays empty when no image of the sub-batch has a window: jpgpu_batch_create's own path)
+        std::vector<uint8_t> fl;         // a tensor output: every image's flip
         bool sub_windowed = false;
         for (uint32_t k = first; any_window && k < last; k++) sub_windowed = sub_windowed || win[ok[k]].w != 0;
         for (uint32_t k = first; k < last; k++) {
@@ -834,6 +855,7 @@ int jpgpu_pipeline_decode_windowed(jpgpu_pipeline *p, const uint8_t *const *data
             p->slot[ok[k]] = (int32_t)(k - first);
             descs.push_back(cand[ok[k]]);
             if (sub_windowed) wins.push_back(win[ok[k]]);
+            if (p->tensor) fl.push_back(flips && flips[ok[k]] ? 1 : 0);
         }
         sb.remaining = last - first;
         // Sub-batches of device-entropy images need no pinned staging for coefficients (their entropy-coded bytes are staged by
@@ -841,7 +863,8 @@ int jpgpu_pipeline_decode_windowed(jpgpu_pipeline *p, const uint8_t *const *data
         // would have been 28 GB of pinned host memory.
         const bool staged = j >= n_dev_subs;
         // (another output size: other tables, another output arena — the sub-batch is created anew)
-        bool reuse = sb.batch && descs.size() == sb.descs.size() && sb.compact == compact && (sb.h_coef != nullptr) == staged && sb.rs_w == p->rs_w && sb.rs_h == p->rs_h;
+        bool reuse = sb.batch && descs.size() == sb.descs.size() && sb.compact == compact && (sb.h_coef != nullptr) == staged && sb.rs_w == p->rs_w && sb.rs_h == p->rs_h &&
+                     sb.tensor == p->tensor && (!p->tensor || memcmp(&sb.tn, &p->tn, sizeof(jpgpu_tensor_format)) == 0);  // (... or another tensor format)
         for (size_t k = 0; reuse && k < descs.size(); k++) reuse = same_geometry(descs[k], sb.descs[k]);
         // ... and the same windows: the window group's geometry and the output offsets are made from them (a kept batch with other
         // windows would return the pixels of the old ones).  Other windows for the SAME set of windowed images — a loader's fresh
@@ -858,7 +881,8 @@ int jpgpu_pipeline_decode_windowed(jpgpu_pipeline *p, const uint8_t *const *data
         }
         if (!reuse) {
             sb.drop();
-            rc = p->rs_w ? jpgpu_batch_create_resized(p->device, descs.data(), wins.empty() ? nullptr : wins.data(), p->rs_w, p->rs_h, (uint32_t)descs.size(), JPGPU_BATCH_DEFAULT, &sb.batch)
+            rc = p->tensor ? jpgpu_batch_create_tensor(p->device, descs.data(), wins.empty() ? nullptr : wins.data(), p->rs_w, p->rs_h, &p->tn, (uint32_t)descs.size(), JPGPU_BATCH_DEFAULT, &sb.batch)
+                 : p->rs_w ? jpgpu_batch_create_resized(p->device, descs.data(), wins.empty() ? nullptr : wins.data(), p->rs_w, p->rs_h, (uint32_t)descs.size(), JPGPU_BATCH_DEFAULT, &sb.batch)
                          : jpgpu_batch_create_windowed(p->device, descs.data(), wins.empty() ? nullptr : wins.data(), (uint32_t)descs.size(), JPGPU_BATCH_DEFAULT, &sb.batch);
             if (rc) {
                 // a frame the pixel backend refuses (e.g. an impossible sampling combination) fails the images of
@@ -876,6 +900,8 @@ int jpgpu_pipeline_decode_windowed(jpgpu_pipeline *p, const uint8_t *const *data
             sb.descs = descs;
             sb.wins = wins;
             sb.rs_w = p->rs_w, sb.rs_h = p->rs_h;
+            sb.tensor = p->tensor, sb.tn = p->tn;
+            sb.flips.assign(descs.size(), 0);
             sb.compact = compact;
             sb.h_coef_bytes = jpgpu_batch_coef_arena_bytes(sb.batch);
             if (compact) {  // worst-case compact size per component (12 B/block more than dense), 256-B aligned
@@ -890,6 +916,11 @@ int jpgpu_pipeline_decode_windowed(jpgpu_pipeline *p, const uint8_t *const *data
             }
             if (staged) P_HIP(hipHostMalloc((void **)&sb.h_coef, sb.h_coef_bytes, hipHostMallocDefault));
             else sb.h_coef_bytes = 0;
+        }
+        if (p->tensor && fl != sb.flips) {  // (other flips, kept or new: set in place — a field of the job records, no size or offset changes)
+            rc = jpgpu_batch_set_flips(sb.batch, fl.data());
+            if (rc) return jpgpu::set_err(p->err, rc, "%s", jpgpu_batch_last_error(sb.batch));
+            sb.flips = fl;
         }
         if (download && (!sb.h_out || sb.h_out_bytes < jpgpu_batch_out_arena_bytes(sb.batch))) {
             if (sb.h_out) (void)hipHostFree(sb.h_out);
@@ -1416,6 +1447,15 @@ int jpgpu_pipeline_set_output_size(jpgpu_pipeline *p, uint16_t width, uint16_t h
     p->rs_h = height;
     return JPGPU_OK;
 }
+int jpgpu_pipeline_set_tensor_output(jpgpu_pipeline *p, const jpgpu_tensor_format *format) {
+    if (!p) return JPGPU_ERR_FORMAT;
+    if (format && (jpgpu::tensor_elem_bytes(format->dtype) == 0 || format->reserved != 0))
+        return jpgpu::set_err(p->err, JPGPU_ERR_FORMAT, "tensor format: dtype %u, reserved %u (dtype must be 1..3, reserved 0)", format->dtype, format->reserved);
+    for (jpgpu_pipeline *c : p->children) jpgpu_pipeline_set_tensor_output(c, format);
+    p->tensor = format != nullptr;
+    p->tn = format ? *format : jpgpu_tensor_format{};
+    return JPGPU_OK;
+}
 uint32_t jpgpu_pipeline_device_count(const jpgpu_pipeline *p) { return !p ? 0u : (p->children.empty() ? 1u : (uint32_t)p->children.size()); }
 int jpgpu_pipeline_image_device(const jpgpu_pipeline *p, uint32_t i) {
     if (!p) return -1;
@@ -1653,7 +1693,8 @@ int jpgpu_pipeline_last_timings(const jpgpu_pipeline *p, jpgpu_pipeline_timings 
 // copy of one sub-batch runs while the next ones decode; nothing to reduce — SURVEY 8e); jpgpu_pipeline_pixels_device then points
 // into the copies.  gather_ms = what the call still waited for the copies after the last child had decoded (the exposed part),
 // gather_copy_ms = the longest child's summed copy time (events around each copy).
-static int multi_decode(jpgpu_pipeline *p, const uint8_t *const *data, const size_t *len, const jpgpu_window *windows, uint32_t n, uint32_t flags) {
+static int multi_decode(jpgpu_pipeline *p, const uint8_t *const *data, const size_t *len, const jpgpu_window *windows, const uint8_t *flips, uint32_t n,
+                        uint32_t flags) {
     const double t0 = now_ms(), cpu0 = process_cpu_ms();
     const uint32_t nc = (uint32_t)p->children.size();
     const bool gather = (flags & JPGPU_PIPELINE_GATHER) != 0;
@@ -1666,10 +1707,12 @@ static int multi_decode(jpgpu_pipeline *p, const uint8_t *const *data, const siz
     std::vector<std::vector<const uint8_t *>> cd(nc);
     std::vector<std::vector<size_t>> cl(nc);
     std::vector<std::vector<jpgpu_window>> cw(nc);
+    std::vector<std::vector<uint8_t>> cf(nc);
     for (uint32_t i = 0; i < n; i++) {
         cd[i % nc].push_back(data[i]);
         cl[i % nc].push_back(len[i]);
         if (windows) cw[i % nc].push_back(windows[i]);
+        if (flips) cf[i % nc].push_back(flips[i]);
     }
     std::vector<int> rcs(nc, JPGPU_OK);
     std::vector<std::thread> th;
@@ -1678,7 +1721,8 @@ static int multi_decode(jpgpu_pipeline *p, const uint8_t *const *data, const siz
         p->children[k]->gather_device = p->device;
         th.emplace_back([&, k] {
             pin_to(p->child_cpus[k]);  // (the call's uploader thread starts from here and inherits the mask)
-            rcs[k] = jpgpu_pipeline_decode_windowed(p->children[k], cd[k].data(), cl[k].data(), windows ? cw[k].data() : nullptr, (uint32_t)cd[k].size(), child_flags);
+            rcs[k] = jpgpu_pipeline_decode_augmented(p->children[k], cd[k].data(), cl[k].data(), windows ? cw[k].data() : nullptr, flips ? cf[k].data() : nullptr,
+                                                     (uint32_t)cd[k].size(), child_flags);
         });
     }
     for (auto &t : th) t.join();

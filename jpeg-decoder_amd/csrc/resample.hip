@@ -1,5 +1,6 @@
-// resample.hip — the resample kernel of jpgpu_batch_create_resized (resample_band.hpp): one launch, every image of the batch in it.
-#include "resample_band.hpp"
+// resample.hip — the resample kernels of jpgpu_batch_create_resized (resample_band.hpp) and jpgpu_batch_create_tensor (tensor_band.hpp):
+// one launch, every image of the batch in it.
+#include "tensor_band.hpp"
 
 namespace jpgpu {
 
@@ -42,6 +43,53 @@ hipError_t launch_resample_band(const ResampleJob *d_jobs, const int32_t *d_tab,
     const uint64_t wgs = (((uint64_t)n_images + 7u) / 8u) * 8u * max_bands;
     if (wgs > 0x7fffffffull) return hipErrorInvalidValue;
     resample_band_kernel<<<dim3((uint32_t)wgs), dim3(RS_NT), lds_bytes, stream>>>(d_jobs, d_tab, max_bands, n_images);
+    return hipGetLastError();
+}
+
+// The same grid, bands, chunks and horizontal pass; the vertical pass writes the image's tensor (tensor_band.hpp).  E: the element's bits.
+template <class E>
+__global__ __launch_bounds__(RS_NT, 4) void resample_tensor_kernel(const TensorJob *__restrict__ jobs, const int32_t *__restrict__ tab_,
+                                                                const uint32_t *__restrict__ ttab_, uint32_t max_bands, uint32_t n_images) {
+    extern __shared__ __attribute__((aligned(16))) uint8_t lds_raw[];
+    const uint32_t xcd = blockIdx.x & 7u, slot = blockIdx.x >> 3, image = (slot / max_bands) * 8u + xcd, band = slot % max_bands;
+    if (image >= n_images) return;
+    const TensorJob t = jobs[image];
+    if (band >= t.r.bands) return;  // (uniform)
+    const JP_GLOBAL int32_t *tab = (const JP_GLOBAL int32_t *)tab_;
+    const uint32_t chunks = RBand::chunks_of(t.r, tab, band), tid = threadIdx.x;
+    TBand<E>::load_table(t, (const JP_GLOBAL uint32_t *)ttab_, tid, lds_raw);
+    if (chunks == 1u) {  // (uniform)
+        RBand::hpass(t.r, tab, band, 0u, 0u, t.r.out_w, tid, lds_raw);
+        __syncthreads();
+        TBand<E>::vstore(t, tab, band, tid, lds_raw);
+        return;
+    }
+    const uint32_t groups = TBand<E>::groups_of(t, band);
+    for (uint32_t group = 0; group < groups; group++) {
+        uint32_t x0, x1;
+        TBand<E>::group_columns(t, band, group, x0, x1);
+        int32_t sum[16] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+        for (uint32_t chunk = 0; chunk < chunks; chunk++) {
+            __syncthreads();  // (the vertical pass before has read its rows; the table is in place)
+            RBand::hpass(t.r, tab, band, chunk, x0, x1, tid, lds_raw);
+            __syncthreads();
+            TBand<E>::vacc(t, tab, band, chunk, group, tid, lds_raw, sum);
+        }
+        TBand<E>::vput(t, band, group, tid, sum, lds_raw);
+    }
+}
+
+hipError_t launch_resample_tensor(const TensorJob *d_jobs, const int32_t *d_tab, const void *d_ttab, uint32_t elem_bytes, uint32_t n_images, uint32_t max_bands,
+                                  uint32_t lds_bytes, hipStream_t stream) {
+    if (n_images == 0 || max_bands == 0) return hipSuccess;
+    if (lds_bytes > RS_MAX_LDS || (elem_bytes != 2u && elem_bytes != 4u)) return hipErrorInvalidValue;
+    const uint64_t wgs = (((uint64_t)n_images + 7u) / 8u) * 8u * max_bands;
+    if (wgs > 0x7fffffffull) return hipErrorInvalidValue;
+    const uint32_t lds = ((lds_bytes + 15u) & ~15u) + 4u * 256u * elem_bytes;  // the rows, then the table
+    if (elem_bytes == 4u)
+        resample_tensor_kernel<uint32_t><<<dim3((uint32_t)wgs), dim3(RS_NT), lds, stream>>>(d_jobs, d_tab, (const uint32_t *)d_ttab, max_bands, n_images);
+    else
+        resample_tensor_kernel<uint16_t><<<dim3((uint32_t)wgs), dim3(RS_NT), lds, stream>>>(d_jobs, d_tab, (const uint32_t *)d_ttab, max_bands, n_images);
     return hipGetLastError();
 }
 

@@ -9,7 +9,7 @@ import ctypes as C
 import numpy as np
 
 from . import _native as N
-from .batch import output_size_pair, window_structs
+from .batch import flip_bytes, output_size_pair, window_structs
 from .decoder import CODING_PROCESSES, PIXEL_FORMATS, ImageInfo
 from .error import check, error_for_status
 from .worker import color_transform_id
@@ -75,7 +75,8 @@ class Pipeline:
     __del__ = close
 
     def decode(self, streams, download=True, dense=False, device_entropy=True, scale=None, color_transform=None, max_decoding_buffer_size=None,
-               gather=False, host_light=None, input_pinned=False, progressive_on_host=False, windows=None, output_size=None):
+               gather=False, host_light=None, input_pinned=False, progressive_on_host=False, windows=None, output_size=None,
+               tensor=None, flips=None):
         """-> list with, per stream, a numpy uint8 array of the decoded pixels (``Decoder.decode()``'s Vec<u8>) or the
         ``Error`` instance that stream produced.  download=False leaves the pixels in HBM (see ``device_pointer``); dense=True sends all
         64 coefficients of every block over PCIe instead of the compact form (same pixels, A/B switch); device_entropy=True
@@ -98,7 +99,12 @@ class Pipeline:
         are the 8-bit bilinear resample with antialiasing (Pillow's ``Image.resize((w, h), BILINEAR)`` arithmetic on the cropped image,
         DESIGN.md §4.10) of what it gives without — its window or its whole output — so every array is h * w * nc bytes and only those
         cross the link; a stream with planar output (color_transform "None", more than one component) fails alone (UnsupportedError);
-        ``timings()["images_resized"]`` counts the streams."""
+        ``timings()["images_resized"]`` counts the streams.
+        tensor: None or a ``TensorFormat`` (jpgpu_pipeline_set_tensor_output, set on every call; needs output_size, else FormatError): every
+        stream's result is its resized pixels normalised and channel-first, an array of shape (nc, h, w) of the format's dtype (np.uint16
+        bit patterns for bfloat16) written by the resample itself; ``download(i)`` / ``pixels_host(i)`` return the same.
+        flips: None or one truth value per stream: that stream's columns mirrored (needs `tensor`, else FormatError and nothing is
+        decoded).  Fresh windows and flips for the same files keep the pipeline's sub-batches."""
         if isinstance(streams, PinnedFiles):
             bufs = None
             n = len(streams)
@@ -109,11 +115,16 @@ class Pipeline:
             n = len(bufs)
         wins = window_structs(windows, n)  # (raises on a list of the wrong length, before anything native is called)
         size = (0, 0) if output_size is None else output_size_pair(output_size)
+        flip_arr = flip_bytes(flips, n)
+        fmt = None if tensor is None else tensor.struct()
+        self._shape = None if tensor is None else (tensor.numpy_dtype, size[1], size[0])
         L = N.lib()
         check(L.jpgpu_pipeline_set_max_decoding_buffer_size(self._h, (1 << 64) - 1 if max_decoding_buffer_size is None else int(max_decoding_buffer_size)), b"set_max")
         check(L.jpgpu_pipeline_set_color_transform(self._h, color_transform_id(color_transform) if color_transform is not None else -1), b"set_color_transform")
         check(L.jpgpu_pipeline_set_scale(self._h, *((int(scale[0]), int(scale[1])) if scale else (0, 0))), b"set_scale")
         st = L.jpgpu_pipeline_set_output_size(self._h, *size)
+        check(st, L.jpgpu_pipeline_last_error(self._h) if st else b"")
+        st = L.jpgpu_pipeline_set_tensor_output(self._h, None if fmt is None else C.byref(fmt))
         check(st, L.jpgpu_pipeline_last_error(self._h) if st else b"")
         if bufs is None:
             ptrs = (C.c_void_p * max(n, 1))(*[streams.base + o for o in streams.offsets])
@@ -125,7 +136,9 @@ class Pipeline:
         flags = ((N.PIPELINE_DOWNLOAD if download else 0) | (N.PIPELINE_DENSE if dense else 0) | (N.PIPELINE_DEVICE_ENTROPY if device_entropy else 0) |
                  (N.PIPELINE_GATHER if gather else 0) | (N.PIPELINE_INPUT_PINNED if input_pinned else 0) | (N.PIPELINE_PROGRESSIVE_ON_HOST if progressive_on_host else 0) |
                  (0 if host_light is None else (N.PIPELINE_HOST_LIGHT if host_light else N.PIPELINE_HOST_STAGED)))
-        if wins is None:
+        if flip_arr is not None:
+            st = L.jpgpu_pipeline_decode_augmented(self._h, C.cast(ptrs, C.POINTER(C.c_void_p)), lens, wins, flip_arr, n, flags)
+        elif wins is None:
             st = L.jpgpu_pipeline_decode(self._h, C.cast(ptrs, C.POINTER(C.c_void_p)), lens, n, flags)
         else:
             st = L.jpgpu_pipeline_decode_windowed(self._h, C.cast(ptrs, C.POINTER(C.c_void_p)), lens, wins, n, flags)
@@ -139,11 +152,18 @@ class Pipeline:
             nbytes = L.jpgpu_pipeline_pixel_bytes(self._h, i)
             if download and not keep_pinned:
                 p = L.jpgpu_pipeline_pixels_host(self._h, i)
-                out.append(np.ctypeslib.as_array(C.cast(p, C.POINTER(C.c_uint8)), shape=(nbytes,)).copy() if nbytes else
+                out.append(self._shaped(np.ctypeslib.as_array(C.cast(p, C.POINTER(C.c_uint8)), shape=(nbytes,)).copy()) if nbytes else
                            np.zeros(0, np.uint8))
             else:
                 out.append(nbytes)
         return out
+
+    def _shaped(self, flat):
+        """A stream's bytes as the last call's tensor format shapes them: (nc, h, w) of its dtype; flat uint8 without one."""
+        shape = getattr(self, "_shape", None)
+        if shape is None:
+            return flat
+        return flat.view(shape[0]).reshape(-1, shape[1], shape[2])
 
     def info(self, image):
         i = N.ImageInfoStruct()
@@ -166,7 +186,7 @@ class Pipeline:
         got = C.c_size_t(0)
         st = N.lib().jpgpu_pipeline_download(self._h, image, out.ctypes.data, out.size, C.byref(got))
         check(st, N.lib().jpgpu_pipeline_last_error(self._h) if st else b"")
-        return out[: got.value]
+        return self._shaped(out[: got.value])
 
     def pixels_host(self, image):
         """View (no copy) of one image's pixels in the pipeline's pinned host buffer after a call with download=True / "pinned";
@@ -175,7 +195,7 @@ class Pipeline:
         p = N.lib().jpgpu_pipeline_pixels_host(self._h, image)
         if not p or not n:
             return None
-        return np.ctypeslib.as_array(C.cast(p, C.POINTER(C.c_uint8)), shape=(n,))
+        return self._shaped(np.ctypeslib.as_array(C.cast(p, C.POINTER(C.c_uint8)), shape=(n,)))
 
     def device_pointer(self, image):
         return N.lib().jpgpu_pipeline_pixels_device(self._h, image)
