@@ -44,6 +44,8 @@ def lib():
         L.emu_chunk_shift.restype = C.c_uint32
         L.emu_huff_set_launch.argtypes = [C.c_uint32, C.c_uint32, C.c_uint32]
         L.emu_huff_set_launch.restype = None
+        L.emu_huff_set_chunking.argtypes = [C.c_uint32, C.c_uint32, C.c_uint32]
+        L.emu_huff_set_chunking.restype = None
         L.emu_huff_decode.argtypes = [C.c_void_p, C.c_size_t, C.POINTER(C.c_void_p), C.POINTER(C.c_uint32)]
         L.emu_prog_plan.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
         L.emu_prog_decode.argtypes = [C.c_void_p, C.c_size_t, C.POINTER(C.c_void_p), C.c_int]

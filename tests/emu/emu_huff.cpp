@@ -16,6 +16,7 @@ using jpgpu::host::PlannedScan;
 static uint32_t g_sync_iters = 1, g_sync_wg = 256, g_sync_stale = 0;  // launch shape of the sync passes (emu_huff_set_launch)
 static uint32_t g_late = 2;  // HuffSyncJob::late_pass (emu_huff_set_late)
 static uint32_t g_tail = 8;  // eighths of its chunk a lane walks in sync pass 0 (HuffSyncJob::pass0_skip)
+static uint32_t g_chunk_blocks = 48, g_chunk_min_shift = 10, g_max_launches = 32;  // chunking and launches (emu_huff_set_chunking; batch_entropy.cpp picks them per call)
 static uint32_t g_dri_shift = 0;  // restart segments in chunk slots: forced chunk size (emu_huff_set_dri; 0: the product's choice)
 static uint32_t g_emit_mismatch = 0;
 static uint32_t g_range[2] = {0, 0};  // by-product of the last emu_huff_decode: largest |DC * q| / |AC * q| written (range_stats.hpp)
@@ -97,6 +98,13 @@ int emu_stage_segment_clean(uint8_t* dst, const uint8_t* src, uint32_t n) {
 uint32_t emu_chunk_shift(uint32_t stuffed_bytes, uint32_t total_blocks) { return huff_sync_chunk_shift(stuffed_bytes, total_blocks); }
 
 void emu_huff_set_dri(uint32_t shift) { g_dri_shift = shift; }
+// blocks per chunk aimed at, smallest chunk (1 << min_shift bits), launches a scan is given: 48 / 10 / 32 by default; a small call of the
+// product gets 12 / 9 / 16 (two passes each)
+void emu_huff_set_chunking(uint32_t blocks, uint32_t min_shift, uint32_t launches) {
+    g_chunk_blocks = blocks ? blocks : 48u;
+    g_chunk_min_shift = min_shift ? min_shift : 10u;
+    g_max_launches = launches ? launches : 32u;
+}
 void emu_huff_set_late(uint32_t pass) { g_late = pass; }
 void emu_huff_set_tail(uint32_t eighths) { g_tail = eighths >= 1 && eighths <= 8 ? eighths : 8; }
 void emu_huff_last_range(uint32_t out[2]) { out[0] = g_range[0], out[1] = g_range[1]; }
@@ -304,7 +312,7 @@ extern "C" int emu_huff_decode(const uint8_t* data, size_t len, int16_t* const* 
                     stuffed += ps.seg_off[sg + 1] - ps.seg_off[sg];
                     longest = std::max<uint32_t>(longest, ps.seg_off[sg + 1] - ps.seg_off[sg]);
                 }
-                sj.chunk_shift = g_dri_shift ? g_dri_shift : huff_sync_chunk_shift(stuffed, sj.bpm * ps.n_mcu);
+                sj.chunk_shift = g_dri_shift ? g_dri_shift : huff_sync_chunk_shift(stuffed, sj.bpm * ps.n_mcu, g_chunk_blocks, g_chunk_min_shift);
                 sj.seg_off = table.data();
                 sj.n_seg = (uint32_t)(ps.seg_off.size() / 2);
                 sj.ri = ps.ri;
@@ -312,7 +320,7 @@ extern "C" int emu_huff_decode(const uint8_t* data, size_t len, int16_t* const* 
                 sj.n_chunks = sj.n_seg * sj.seg_chunks;
                 sj.n_bits = 0;
             } else {
-                sj.chunk_shift = huff_sync_chunk_shift(ps.seg_off[1] - ps.seg_off[0], sj.bpm * ps.n_mcu);
+                sj.chunk_shift = huff_sync_chunk_shift(ps.seg_off[1] - ps.seg_off[0], sj.bpm * ps.n_mcu, g_chunk_blocks, g_chunk_min_shift);
                 sj.n_chunks = huff_sync_chunks(table[1], sj.chunk_shift);
             }
             sj.pass0_skip = ((1u << sj.chunk_shift) >> 3) * (8u - g_tail);
@@ -354,7 +362,7 @@ extern "C" int emu_huff_decode(const uint8_t* data, size_t len, int16_t* const* 
             // launch, the least the device guarantees.
             const uint32_t iters = g_sync_iters, WG = g_sync_wg;
             uint32_t pass = 0, launch = 0;
-            for (; launch < 32; launch++) {
+            for (; launch < g_max_launches; launch++) {
                 changed = 0;
                 const uint32_t n_wg = (sj.n_chunks + WG - 1) / WG;
                 for (uint32_t w = n_wg; w-- > 0;) {
@@ -378,7 +386,7 @@ extern "C" int emu_huff_decode(const uint8_t* data, size_t len, int16_t* const* 
                 if (launch > 0 && changed == 0) break;
             }
             pass = launch;
-            if (pass == 32) status |= 1u | 64u;
+            if (pass == g_max_launches) status |= 1u | 64u;
             if (sj.n_seg > 1u) {  // (huff_sync_scan_kernel, restart segments: one thread per segment)
                 for (uint32_t seg = 0; seg < sj.n_seg; seg++) status |= huff_emit_segment_scan(sj, seg);
                 if (emit_buf.back() != 0xABABABABu) status |= 0x8000u;
