@@ -141,6 +141,7 @@ enum {
     JPGPU_BATCH_EXTERNAL_BUFFERS = 1, /* caller binds device memory (e.g. torch tensors)   */
     JPGPU_BATCH_FORCE_GENERIC = 2,    /* never take the fused fast paths (two-kernel path)  */
     JPGPU_BATCH_ASSUME_HOSTILE = 4,   /* skip the range scan: always use the exact 32-bit path */
+    JPGPU_BATCH_RGB_OUTPUT = 8,       /* with an output size: every image gives three channels (see below) */
 };
 
 int jpgpu_batch_create(int device, const jpgpu_image_desc *descs, uint32_t n_images,
@@ -219,6 +220,23 @@ typedef struct jpgpu_tensor_format {
 } jpgpu_tensor_format;
 int jpgpu_batch_create_tensor(int device, const jpgpu_image_desc *descs, const jpgpu_window *windows, uint16_t out_w, uint16_t out_h,
                               const jpgpu_tensor_format *format, uint32_t n_images, uint32_t flags, jpgpu_batch **out);
+/* ---- RGB output: three channels for every image of a resized / tensor batch (JPGPU_BATCH_RGB_OUTPUT) -----------------------------
+ * With the flag, jpgpu_batch_create_resized and jpgpu_batch_create_tensor give every image three channels — out_h * out_w * 3 bytes,
+ * interleaved, or 3 x out_h x out_w elements — so the arena of N images to 224 x 224 IS one N x 3 x 224 x 224 tensor whatever the
+ * files hold.  The result is convert, then crop, then resample — Image.open(f).convert("RGB") followed by the crop and resize:
+ *     rgb(src) -> the resample above, unchanged -> (the table lookup and flip above, unchanged, with 3 channels)
+ * where src is what the image gives without an output size (its window, or all of it, nc_src channels) and
+ *   nc_src == 3 (YCbCr, RGB):  rgb(src) = src.
+ *   nc_src == 1 (gray):        R = G = B = v.
+ *   nc_src == 4 (CMYK, YCCK; ink amounts, 0 = no ink — Pillow's mode "CMYK"): Pillow's cmyk2rgb per pixel, in 32-bit integers:
+ *       nk = 255 - K;   for X in (C, M, Y):  t = X * nk + 128;  md = ((t >> 8) + t) >> 8;  out = nk - md
+ *     (= (2 (255 - X)(255 - K) + 255) / 510 rounded down; no clamp: md <= nk).  Not linear: applied to the source pixels BEFORE the
+ *     horizontal pass.
+ * Only the resample launch differs (jpgpu_batch_path gains "+rgb" before "+resize"): the batch's other kernels write L8 / RGB24 /
+ * CMYK32 to the intermediate arena as without the flag.  A tensor format's mean[c] and std[c] are checked for c < 3 and the table is
+ * jpgpu_tensor_table(format, 3, ...) for every image: a gray image's three planes differ through T[c].  Without the flag nothing
+ * changes.  Refusals: the flag on jpgpu_batch_create / _create_windowed (no output size): JPGPU_ERR_UNSUPPORTED with the reason in
+ * jpgpu_batch_last_error; planar ColorTransform None images stay JPGPU_ERR_UNSUPPORTED. */
 /* The flip flag of every image (`flips`: n_images bytes, non-zero = mirrored; NULL: none) from the next jpgpu_batch_decode on: a
  * field of the image's job record, sent with the job tables.  Never changes a size or an offset.  JPGPU_ERR_UNSUPPORTED on a batch
  * without a tensor format. */

@@ -240,6 +240,14 @@ int jpgpu_pipeline_set_output_size(jpgpu_pipeline *p, uint16_t width, uint16_t h
  * tensor's bytes; timings.images_resized counts the images.  A change of the format between calls creates the kept sub-batches anew,
  * as a changed output size does. */
 int jpgpu_pipeline_set_tensor_output(jpgpu_pipeline *p, const jpgpu_tensor_format *format);
+/* RGB output for every image of the calls that follow (sticky, like the output size; 0: off, the default — same routes, kernels,
+ * launches and bytes as ever): the sub-batches are created with JPGPU_BATCH_RGB_OUTPUT (jpgpu.h), so every image — gray, CMYK and YCCK
+ * files among them — gives height * width * 3 bytes, or a 3 x height x width tensor whose format is checked for three channels.  It
+ * needs an output size: with none in force the next decode fails as a whole with JPGPU_ERR_FORMAT before anything is decoded.
+ * jpgpu_pipeline_pixel_bytes / _pixels_device / _pixels_host / _download, the pinned block, the gather copies and timings.pixel_bytes
+ * hold / count the three-channel bytes; jpgpu_pipeline_image_info keeps reporting the file's own components and pixel format.
+ * Switching it on or off between calls creates the kept sub-batches anew, as a changed output size does. */
+int jpgpu_pipeline_set_rgb_output(jpgpu_pipeline *p, int on);
 /* Decoder::set_color_transform (src/decoder.rs:158-161) for every image of the calls that follow: one of the JPGPU_CT_* values of
  * jpgpu.h instead of what determine_color_transform finds per image; a negative value: per image again (the default). */
 int jpgpu_pipeline_set_color_transform(jpgpu_pipeline *p, int color_transform);

@@ -30,7 +30,7 @@ HEADER_PATH = os.path.join(_ROOT, "include", "jpgpu.h")
 OK, ERR_FORMAT, ERR_UNSUPPORTED, ERR_IO, ERR_INTERNAL, ERR_NO_DEVICE = range(6)
 MAX_COMPONENTS = 4
 
-BATCH_DEFAULT, BATCH_EXTERNAL_BUFFERS, BATCH_FORCE_GENERIC, BATCH_ASSUME_HOSTILE = 0, 1, 2, 4
+BATCH_DEFAULT, BATCH_EXTERNAL_BUFFERS, BATCH_FORCE_GENERIC, BATCH_ASSUME_HOSTILE, BATCH_RGB_OUTPUT = 0, 1, 2, 4, 8
 
 
 class Component(C.Structure):
@@ -207,6 +207,7 @@ _PROTOS = {
     "jpgpu_pipeline_set_scale": (C.c_int, [C.c_void_p, C.c_uint16, C.c_uint16]),
     "jpgpu_pipeline_set_output_size": (C.c_int, [C.c_void_p, C.c_uint16, C.c_uint16]),
     "jpgpu_pipeline_set_tensor_output": (C.c_int, [C.c_void_p, C.POINTER(TensorFormatStruct)]),
+    "jpgpu_pipeline_set_rgb_output": (C.c_int, [C.c_void_p, C.c_int]),
     "jpgpu_pipeline_set_color_transform": (C.c_int, [C.c_void_p, C.c_int]),
     "jpgpu_pipeline_set_max_decoding_buffer_size": (C.c_int, [C.c_void_p, C.c_size_t]),
     "jpgpu_pipeline_download": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]),

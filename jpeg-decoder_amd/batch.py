@@ -124,14 +124,21 @@ class Batch:
     its resized pixels normalised and channel-first: nc x h x w elements of the format's dtype, written by the resample itself;
     out_bytes / out_offset / the output arena hold them, ``download(i)`` returns an array of shape (nc, h, w) (np.uint16 bit patterns
     for bfloat16), `path` ends in "+resize+tensor".  ``set_flips([...])`` mirrors images' columns from the next decode on.  Images of
-    3 x 224 x 224 follow each other without a gap: a ``torch.empty(N, 3, 224, 224)`` bound with BATCH_EXTERNAL_BUFFERS is the result."""
+    3 x 224 x 224 follow each other without a gap: a ``torch.empty(N, 3, 224, 224)`` bound with BATCH_EXTERNAL_BUFFERS is the result.
 
-    def __init__(self, descs, device=0, flags=N.BATCH_DEFAULT, windows=None, output_size=None, tensor=None):
+    rgb: True adds BATCH_RGB_OUTPUT (needs an output_size, else UnsupportedError): every image gives three channels — gray replicated,
+    CMYK / YCCK through Pillow's integer cmyk2rgb, before the resample (``Image.convert("RGB")`` then crop and resize)
+    — so arrays are (h * w * 3,) uint8 or (3, h, w) whatever the files hold; `path` gains "+rgb" before "+resize"."""
+
+    def __init__(self, descs, device=0, flags=N.BATCH_DEFAULT, windows=None, output_size=None, tensor=None, rgb=False):
         self._h = C.c_void_p()
         arr = (N.ImageDesc * len(descs))(*descs)
         wins = window_structs(windows, len(descs))
         self.output_size = None if output_size is None else output_size_pair(output_size)
         self.tensor = tensor
+        self.rgb = bool(rgb) or bool(flags & N.BATCH_RGB_OUTPUT)
+        if rgb:
+            flags |= N.BATCH_RGB_OUTPUT
         if tensor is not None:
             w, h = self.output_size if self.output_size is not None else (0, 0)
             fmt = tensor.struct()

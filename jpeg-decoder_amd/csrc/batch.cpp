@@ -39,6 +39,7 @@ static int batch_resample_tables(jpgpu_batch *b) {
         window_grid(d.components, d.ncomp, d.out_w, d.out_h, j.in_w, j.in_h);
         if (k < b->win.ids.size() && b->win.ids[k] == i) j.in_w = b->win.geoms[k].ww, j.in_h = b->win.geoms[k].wh, k++;
         j.nc = d.ncomp, j.out_w = b->rs_w, j.out_h = b->rs_h;
+        if (b->flags & JPGPU_BATCH_RGB_OUTPUT) j.nc = 3u, j.src_nc = d.ncomp == 3u ? 0u : d.ncomp;  // (gray / CMYK: converted by the horizontal pass)
         if (!axis(j.in_w, j.out_w, j.hb, j.hk, j.hks) || !axis(j.in_h, j.out_h, j.vb, j.vk, j.vks))
             return set_err(b->err, JPGPU_ERR_UNSUPPORTED, "image %u: resample tables of the batch exceed 2^32 words", i);
     }
@@ -182,10 +183,13 @@ static int batch_create(int device, const jpgpu_image_desc *descs, const jpgpu_w
     const bool resized = rs_w != 0 || rs_h != 0;
     if (resized && (rs_w == 0 || rs_h == 0 || rs_w > RS_MAX_OUT || rs_h > RS_MAX_OUT))
         return set_err(b->err, JPGPU_ERR_FORMAT, "output size %ux%u: width and height must be 1..%u", rs_w, rs_h, RS_MAX_OUT);
+    const bool rgb = (flags & JPGPU_BATCH_RGB_OUTPUT) != 0;  // (every image gives three channels: the resample converts gray and CMYK)
+    if (rgb && !resized)
+        return set_err(b->err, JPGPU_ERR_UNSUPPORTED, "JPGPU_BATCH_RGB_OUTPUT needs an output size (jpgpu_batch_create_resized / _create_tensor)");
     if (tensor) {  // (the format against the channels of every image of the call, before anything is allocated)
         if (!resized) return set_err(b->err, JPGPU_ERR_FORMAT, "a tensor format needs an output size");
-        uint32_t nc_max = 1;
-        for (uint32_t i = 0; i < n_images; i++) nc_max = std::max(nc_max, std::min<uint32_t>(descs[i].ncomp, 4u));
+        uint32_t nc_max = rgb ? 3u : 1u;
+        for (uint32_t i = 0; i < n_images && !rgb; i++) nc_max = std::max(nc_max, std::min<uint32_t>(descs[i].ncomp, 4u));
         const char *why = nullptr;
         if (!tensor_format_ok(tensor->dtype, tensor->reserved, tensor->mean, tensor->std, nc_max, why)) return set_err(b->err, JPGPU_ERR_FORMAT, "tensor format: %s", why);
     }
@@ -217,6 +221,7 @@ static int batch_create(int device, const jpgpu_image_desc *descs, const jpgpu_w
         b->out_full_len[i] = out_len;
         if (resized && ij.color_fn == CC_NONE && d.ncomp > 1)
             return set_err(b->err, JPGPU_ERR_UNSUPPORTED, "image %u: no output size for planar output (ColorTransform None with %u components)", i, d.ncomp);
+        if (rgb && d.ncomp != 1 && d.ncomp != 3 && d.ncomp != 4) return set_err(b->err, JPGPU_ERR_UNSUPPORTED, "image %u: no RGB output for %u components", i, d.ncomp);
         // a window smaller than the image: the window group (an empty window or one that covers the image is no window)
         bool windowed = false;
         if (windows) {
@@ -269,7 +274,7 @@ static int batch_create(int device, const jpgpu_image_desc *descs, const jpgpu_w
         b->rs_w = rs_w, b->rs_h = rs_h;
         b->pix_off = b->out_off, b->pix_len = b->out_len, b->pix_bytes = b->out_bytes;
         if (tensor) b->tn_es = tensor_elem_bytes(tensor->dtype), b->tn_flips.assign(n_images, 0);
-        for (uint32_t i = 0; i < n_images; i++) lens[i] = (size_t)rs_w * rs_h * b->descs[i].ncomp * (tensor ? b->tn_es : 1u);
+        for (uint32_t i = 0; i < n_images; i++) lens[i] = (size_t)rs_w * rs_h * (rgb ? 3u : b->descs[i].ncomp) * (tensor ? b->tn_es : 1u);
         b->out_bytes = arena_layout(lens, b->out_off, b->out_len);
     }
 
@@ -297,6 +302,7 @@ static int batch_create(int device, const jpgpu_image_desc *descs, const jpgpu_w
     if (!b->scaled.empty()) b->path = (b->fused.empty() && b->generic_ids.empty()) ? b->scaled_name : "mixed";
     if (!b->win.empty()) b->path = b->path.empty() ? "window" : "mixed";
     if (b->path.empty()) b->path = "generic";
+    if (rgb) b->path += "+rgb";
     if (resized) b->path += "+resize";
     if (tensor) b->path += "+tensor";
     const size_t full = arena_layout(b->out_full_len);  // (what the whole images take)
@@ -315,8 +321,8 @@ static int batch_create(int device, const jpgpu_image_desc *descs, const jpgpu_w
             B_HIP(hipMalloc((void **)&b->d_tn_jobs, (size_t)n_images * sizeof(TensorJob)));
             B_HIP(hipMalloc(&b->d_tn_table, TN_TABLE_MAX));
             std::vector<uint32_t> table(TN_TABLE_MAX / 4u, 0u);
-            uint32_t nc_max = 1;
-            for (uint32_t i = 0; i < n_images; i++) nc_max = std::max<uint32_t>(nc_max, b->descs[i].ncomp);
+            uint32_t nc_max = rgb ? 3u : 1u;
+            for (uint32_t i = 0; i < n_images && !rgb; i++) nc_max = std::max<uint32_t>(nc_max, b->descs[i].ncomp);
             tensor_table(tensor->dtype, tensor->mean, tensor->std, nc_max, table.data());
             B_HIP(hipMemcpy(b->d_tn_table, table.data(), TN_TABLE_MAX, hipMemcpyHostToDevice));
         } else {
@@ -835,9 +841,10 @@ int jpgpu_batch_decode(jpgpu_batch *b, void *hip_stream) {
                                  b->win.lds_bytes, b->win.scales, s));
     if (b->tn_es && b->tn_sent) B_HIP(hipStreamWaitEvent(s, b->tn_sent, 0));  // (the jobs may have gone up on another stream than this one)
     if (b->tn_es)  // (a tensor output: the same resample, its vertical pass writes every image's tensor)
-        B_HIP(launch_resample_tensor(b->d_tn_jobs, b->d_rs_tab, b->d_tn_table, b->tn_es, (uint32_t)b->descs.size(), b->rs_max_bands, b->rs_lds_bytes, s));
+        B_HIP(launch_resample_tensor(b->d_tn_jobs, b->d_rs_tab, b->d_tn_table, b->tn_es, (uint32_t)b->descs.size(), b->rs_max_bands, b->rs_lds_bytes, s,
+                                      (b->flags & JPGPU_BATCH_RGB_OUTPUT) != 0));
     else if (b->rs_w)  // (an output size: every image's pixels, wherever the launches above left them in the intermediate arena)
-        B_HIP(launch_resample_band(b->d_rs_jobs, b->d_rs_tab, (uint32_t)b->descs.size(), b->rs_max_bands, b->rs_lds_bytes, s));
+        B_HIP(launch_resample_band(b->d_rs_jobs, b->d_rs_tab, (uint32_t)b->descs.size(), b->rs_max_bands, b->rs_lds_bytes, s, (b->flags & JPGPU_BATCH_RGB_OUTPUT) != 0));
     if (b->phase_events_valid) B_HIP(hipEventRecord(b->ev_phase[5], s));
     return JPGPU_OK;
 }

@@ -260,6 +260,7 @@ struct SubBatch {
     uint16_t rs_w = 0, rs_h = 0;      // the output size the batch was created with (jpgpu_pipeline_set_output_size; 0 x 0: none)
     bool tensor = false;              // the tensor format the batch was created with (jpgpu_pipeline_set_tensor_output), if any
     jpgpu_tensor_format tn{};
+    bool rgb = false;                 // created with JPGPU_BATCH_RGB_OUTPUT (jpgpu_pipeline_set_rgb_output)
     std::vector<uint8_t> flips;       // a tensor batch: the flip of every image as the batch holds it (jpgpu_batch_set_flips)
     uint32_t remaining = 0;  // images not yet uploaded / failed (uploader thread only)
     hipEvent_t ready[kCopyStreams] = {nullptr, nullptr, nullptr, nullptr};
@@ -276,6 +277,7 @@ struct SubBatch {
         wins.clear();
         rs_w = rs_h = 0;
         tensor = false;
+        rgb = false;
         flips.clear();
     }
 };
@@ -318,6 +320,7 @@ struct jpgpu_pipeline {
     uint16_t req_w = 0, req_h = 0;  // jpgpu_pipeline_set_scale (0 x 0: full size)
     uint16_t rs_w = 0, rs_h = 0;    // jpgpu_pipeline_set_output_size (0 x 0: none)
     bool tensor = false;            // jpgpu_pipeline_set_tensor_output
+    bool rgb = false;               // jpgpu_pipeline_set_rgb_output
     jpgpu_tensor_format tn{};
     int color_transform = -1;       // jpgpu_pipeline_set_color_transform (< 0: what every image says itself)
     size_t max_bytes = SIZE_MAX;    // jpgpu_pipeline_set_max_decoding_buffer_size
@@ -638,6 +641,7 @@ int jpgpu_pipeline_decode_augmented(jpgpu_pipeline *p, const uint8_t *const *dat
     if (p && (flags & ~kKnownFlags)) return jpgpu::set_err(p->err, JPGPU_ERR_FORMAT, "jpgpu_pipeline_decode: unknown flag bits 0x%x (this library: %s)", flags & ~kKnownFlags, jpgpu_version());
     // (a tensor output needs an output size, flips a tensor output: refused before anything is decoded)
     if (p && p->tensor && !p->rs_w) return jpgpu::set_err(p->err, JPGPU_ERR_FORMAT, "jpgpu_pipeline_decode: a tensor output needs an output size (jpgpu_pipeline_set_output_size)");
+    if (p && p->rgb && !p->rs_w) return jpgpu::set_err(p->err, JPGPU_ERR_FORMAT, "jpgpu_pipeline_decode: RGB output needs an output size (jpgpu_pipeline_set_output_size)");
     if (p && flips && !p->tensor) return jpgpu::set_err(p->err, JPGPU_ERR_FORMAT, "jpgpu_pipeline_decode_augmented: flips need a tensor output (jpgpu_pipeline_set_tensor_output)");
     if (p && !p->children.empty()) return (n && (!data || !len)) ? JPGPU_ERR_FORMAT : multi_decode(p, data, len, windows, flips, n, flags);
     if (!p || !p->pool || (n && (!data || !len))) return JPGPU_ERR_FORMAT;
@@ -745,7 +749,7 @@ int jpgpu_pipeline_decode_augmented(jpgpu_pipeline *p, const uint8_t *const *dat
                 if (p->rs_w && planar)
                     throw DecodeError{JPGPU_ERR_UNSUPPORTED, "no output size for planar output (ColorTransform None with more than one component)"};
                 const char *bad = nullptr;  // (the format's means and stds against THIS image's channels)
-                if (p->tensor && !jpgpu::tensor_format_ok(p->tn.dtype, p->tn.reserved, p->tn.mean, p->tn.std, d.ncomp, bad))
+                if (p->tensor && !jpgpu::tensor_format_ok(p->tn.dtype, p->tn.reserved, p->tn.mean, p->tn.std, p->rgb ? 3u : d.ncomp, bad))
                     throw DecodeError{JPGPU_ERR_FORMAT, std::string("tensor format: ") + bad};
             }
             if (device_entropy && p->infos[i].coding_process == JPGPU_CODING_DCT_PROGRESSIVE) {
@@ -864,7 +868,7 @@ int jpgpu_pipeline_decode_augmented(jpgpu_pipeline *p, const uint8_t *const *dat
         const bool staged = j >= n_dev_subs;
         // (another output size: other tables, another output arena — the sub-batch is created anew)
         bool reuse = sb.batch && descs.size() == sb.descs.size() && sb.compact == compact && (sb.h_coef != nullptr) == staged && sb.rs_w == p->rs_w && sb.rs_h == p->rs_h &&
-                     sb.tensor == p->tensor && (!p->tensor || memcmp(&sb.tn, &p->tn, sizeof(jpgpu_tensor_format)) == 0);  // (... or another tensor format)
+                     sb.rgb == p->rgb && sb.tensor == p->tensor && (!p->tensor || memcmp(&sb.tn, &p->tn, sizeof(jpgpu_tensor_format)) == 0);  // (... or another tensor format)
         for (size_t k = 0; reuse && k < descs.size(); k++) reuse = same_geometry(descs[k], sb.descs[k]);
         // ... and the same windows: the window group's geometry and the output offsets are made from them (a kept batch with other
         // windows would return the pixels of the old ones).  Other windows for the SAME set of windowed images — a loader's fresh
@@ -881,8 +885,9 @@ int jpgpu_pipeline_decode_augmented(jpgpu_pipeline *p, const uint8_t *const *dat
         }
         if (!reuse) {
             sb.drop();
-            rc = p->tensor ? jpgpu_batch_create_tensor(p->device, descs.data(), wins.empty() ? nullptr : wins.data(), p->rs_w, p->rs_h, &p->tn, (uint32_t)descs.size(), JPGPU_BATCH_DEFAULT, &sb.batch)
-                 : p->rs_w ? jpgpu_batch_create_resized(p->device, descs.data(), wins.empty() ? nullptr : wins.data(), p->rs_w, p->rs_h, (uint32_t)descs.size(), JPGPU_BATCH_DEFAULT, &sb.batch)
+            const uint32_t bf = p->rgb ? JPGPU_BATCH_RGB_OUTPUT : JPGPU_BATCH_DEFAULT;  // (every image three channels: the batch's resample converts)
+            rc = p->tensor ? jpgpu_batch_create_tensor(p->device, descs.data(), wins.empty() ? nullptr : wins.data(), p->rs_w, p->rs_h, &p->tn, (uint32_t)descs.size(), bf, &sb.batch)
+                 : p->rs_w ? jpgpu_batch_create_resized(p->device, descs.data(), wins.empty() ? nullptr : wins.data(), p->rs_w, p->rs_h, (uint32_t)descs.size(), bf, &sb.batch)
                          : jpgpu_batch_create_windowed(p->device, descs.data(), wins.empty() ? nullptr : wins.data(), (uint32_t)descs.size(), JPGPU_BATCH_DEFAULT, &sb.batch);
             if (rc) {
                 // a frame the pixel backend refuses (e.g. an impossible sampling combination) fails the images of
@@ -901,6 +906,7 @@ int jpgpu_pipeline_decode_augmented(jpgpu_pipeline *p, const uint8_t *const *dat
             sb.wins = wins;
             sb.rs_w = p->rs_w, sb.rs_h = p->rs_h;
             sb.tensor = p->tensor, sb.tn = p->tn;
+            sb.rgb = p->rgb;
             sb.flips.assign(descs.size(), 0);
             sb.compact = compact;
             sb.h_coef_bytes = jpgpu_batch_coef_arena_bytes(sb.batch);
@@ -1454,6 +1460,12 @@ int jpgpu_pipeline_set_tensor_output(jpgpu_pipeline *p, const jpgpu_tensor_forma
     for (jpgpu_pipeline *c : p->children) jpgpu_pipeline_set_tensor_output(c, format);
     p->tensor = format != nullptr;
     p->tn = format ? *format : jpgpu_tensor_format{};
+    return JPGPU_OK;
+}
+int jpgpu_pipeline_set_rgb_output(jpgpu_pipeline *p, int on) {
+    if (!p) return JPGPU_ERR_FORMAT;
+    for (jpgpu_pipeline *c : p->children) jpgpu_pipeline_set_rgb_output(c, on);
+    p->rgb = on != 0;
     return JPGPU_OK;
 }
 uint32_t jpgpu_pipeline_device_count(const jpgpu_pipeline *p) { return !p ? 0u : (p->children.empty() ? 1u : (uint32_t)p->children.size()); }

@@ -19,6 +19,9 @@
 //      of four (always when out_w * nc is one) the taps are aligned LDS dword reads, else byte reads.  Sums are exact in int32, so
 //      chunks add up in any order.
 //   4. store: whole aligned dwords; the first / last dword of a band that it shares with its neighbour byte by byte.
+//   5. RGB output (JPGPU_BATCH_RGB_OUTPUT): a job with src_nc = 1 / 4 has a gray / CMYK source and nc = 3; its
+//      horizontal pass (RBand::hpass_walk<1> / hpass_cmyk) converts the source pixels and leaves the three-channel rows in LDS that 2.
+//      leaves for a three-channel source — 1., 3. and 4. run unchanged with nc = 3.
 #pragma once
 #include <stddef.h>
 #include <stdint.h>
@@ -100,11 +103,14 @@ struct ResampleJob {
     uint32_t cap_rows;     // source rows per LDS chunk
     uint32_t pitch;        // LDS row pitch: out_w * nc rounded up to 4
     uint32_t lds_bytes;    // cap_rows * pitch
+    uint32_t src_nc;       // 0: the source has nc channels.  1 / 4 (RGB output; nc is 3 then): the source has src_nc channels,
+                           // the horizontal pass converts them (RBand::hpass_walk<1> / hpass_cmyk) and leaves three-channel rows in LDS
 };
 
 // Plans the bands of a job whose sizes and table offsets are set and whose tables (`tab`, host copy) are filled.  False for sizes the
 // kernel does not run (the batch refuses them before).
 inline bool resample_plan(ResampleJob &j, const int32_t *tab, uint32_t lds_cap = RS_MAX_LDS, uint32_t rb_cap = 64u) {
+    if (j.src_nc != 0 && (j.nc != 3 || (j.src_nc != 1 && j.src_nc != 4))) return false;
     if (j.nc == 0 || j.nc > 4 || j.in_w == 0 || j.in_h == 0 || j.out_w == 0 || j.out_h == 0 || j.out_w > RS_MAX_OUT || j.out_h > RS_MAX_OUT) return false;
     const uint32_t rowb = j.out_w * j.nc;
     j.pitch = (rowb + 3u) & ~3u;
@@ -235,6 +241,136 @@ struct RBand {
         }
     }
 
+    // ---- RGB output: convert, then resample.  The horizontal pass of a source of one or four channels that leaves
+    // the three-channel u8 rows in LDS which hpass leaves for a three-channel source; everything behind it runs with nc = 3. ----
+    // SNC = 1, R = G = B = v: replication commutes with the resample, so one sum per row, its rounded value written three times.
+    // SNC = 3: the source as it is.  The byte walk of hpass (a gray window row starts at any byte) with the channels known.
+    template <uint32_t SNC>
+    static __device__ __forceinline__ void hpass_walk(const ResampleJob &j, const JP_GLOBAL int32_t *tab, uint32_t band, uint32_t chunk, uint32_t x0, uint32_t x1,
+                                                      uint32_t tid, uint8_t *lds) {
+        uint32_t r0, r1, s0, s1;
+        rows_of(j, tab, band, r0, r1, s0, s1);
+        const uint32_t c0 = s0 + chunk * j.cap_rows, c1 = min(c0 + j.cap_rows, s1);
+        if (c0 >= c1 || x0 >= x1) return;
+        const uint32_t nx = x1 - x0, nrows = c1 - c0, units = ((nrows + RS_HROWS - 1u) / RS_HROWS) * nx;
+        const size_t src_pitch = (size_t)j.in_w * SNC;
+        const JP_GLOBAL int32_t *hb = tab + j.hb;
+        const JP_GLOBAL int32_t *hk = tab + j.hk;
+        const JP_GLOBAL uint8_t *src = (const JP_GLOBAL uint8_t *)j.src;
+#pragma unroll 1
+        for (uint32_t u = tid; u < units; u += RS_NT) {
+            const uint32_t rg = u / nx, xx = x0 + (u - rg * nx), row0 = rg * RS_HROWS;
+            const uint32_t xmin = (uint32_t)hb[2u * xx], n = (uint32_t)hb[2u * xx + 1u];
+            const JP_GLOBAL int32_t *k = hk + (size_t)xx * j.hks;
+            const JP_GLOBAL uint32_t *pd[RS_HROWS];
+            uint32_t cur[RS_HROWS], pos[RS_HROWS];
+            int32_t sum[RS_HROWS][SNC];
+#pragma unroll
+            for (uint32_t i = 0; i < RS_HROWS; i++) {
+                const uint32_t row = min(row0 + i, nrows - 1u);
+                const JP_GLOBAL uint8_t *p = src + (size_t)(c0 + row) * src_pitch + (size_t)xmin * SNC;
+                const uint32_t m = (uint32_t)(uintptr_t)p & 3u;
+                pd[i] = reinterpret_cast<const JP_GLOBAL uint32_t *>(p - m);
+                pos[i] = m;
+#pragma unroll
+                for (uint32_t c = 0; c < SNC; c++) sum[i][c] = 1 << (RS_PRECISION_BITS - 1);
+            }
+#pragma unroll
+            for (uint32_t i = 0; i < RS_HROWS; i++) cur[i] = *pd[i];
+#pragma clang loop vectorize(disable) interleave(disable)  // (taps two at a time cost more registers than the kernel has)
+            for (uint32_t x = 0; x < n; x++) {
+                const int32_t kx = k[x];
+#pragma unroll
+                for (uint32_t c = 0; c < SNC; c++) {
+#pragma unroll
+                    for (uint32_t i = 0; i < RS_HROWS; i++) {
+                        if (pos[i] == 4u) {
+                            pd[i]++;
+                            cur[i] = *pd[i];
+                            pos[i] = 0u;
+                        }
+                        sum[i][c] += (int32_t)((cur[i] >> (8u * pos[i])) & 255u) * kx;
+                        pos[i]++;
+                    }
+                }
+            }
+#pragma unroll
+            for (uint32_t i = 0; i < RS_HROWS; i++) {
+                if (row0 + i >= nrows) continue;
+                uint8_t *o = lds + (row0 + i) * j.pitch + xx * 3u;
+#pragma unroll
+                for (uint32_t c = 0; c < SNC; c++) {
+                    int32_t v = sum[i][c] >> RS_PRECISION_BITS;
+                    v = v < 0 ? 0 : (v > 255 ? 255 : v);
+                    if (SNC == 1u) o[0] = o[1] = o[2] = (uint8_t)v;
+                    else o[c] = (uint8_t)v;
+                }
+            }
+        }
+    }
+    // Pillow's cmyk2rgb for one ink X under nk = 255 - K, in 32-bit integers: nk - round(X nk / 255); never outside 0..nk
+    static __device__ __forceinline__ uint32_t cmyk_ink(uint32_t x, uint32_t nk) {
+        const uint32_t t = x * nk + 128u;
+        return nk - (((t >> 8) + t) >> 8);
+    }
+    // four channels (C, M, Y, K ink, 0 = none): a source pixel is one dword — window rows of w * 4 bytes behind a 256-byte aligned
+    // image base are 4-aligned — converted BEFORE it is weighted (the conversion is not linear), three sums per row
+    static __device__ __forceinline__ void hpass_cmyk(const ResampleJob &j, const JP_GLOBAL int32_t *tab, uint32_t band, uint32_t chunk, uint32_t x0, uint32_t x1,
+                                                      uint32_t tid, uint8_t *lds) {
+        uint32_t r0, r1, s0, s1;
+        rows_of(j, tab, band, r0, r1, s0, s1);
+        const uint32_t c0 = s0 + chunk * j.cap_rows, c1 = min(c0 + j.cap_rows, s1);
+        if (c0 >= c1 || x0 >= x1) return;
+        const uint32_t nx = x1 - x0, nrows = c1 - c0, units = ((nrows + RS_HROWS - 1u) / RS_HROWS) * nx;
+        const JP_GLOBAL int32_t *hb = tab + j.hb;
+        const JP_GLOBAL int32_t *hk = tab + j.hk;
+        const JP_GLOBAL uint32_t *src = (const JP_GLOBAL uint32_t *)j.src;
+#pragma unroll 1
+        for (uint32_t u = tid; u < units; u += RS_NT) {
+            const uint32_t rg = u / nx, xx = x0 + (u - rg * nx), row0 = rg * RS_HROWS;
+            const uint32_t xmin = (uint32_t)hb[2u * xx], n = (uint32_t)hb[2u * xx + 1u];
+            const JP_GLOBAL int32_t *k = hk + (size_t)xx * j.hks;
+            const JP_GLOBAL uint32_t *pd[RS_HROWS];
+            int32_t sum[RS_HROWS][3];
+#pragma unroll
+            for (uint32_t i = 0; i < RS_HROWS; i++) {  // (a row beyond the chunk reads the chunk's last)
+                const uint32_t row = min(row0 + i, nrows - 1u);
+                pd[i] = src + (size_t)(c0 + row) * j.in_w + xmin;
+#pragma unroll
+                for (uint32_t c = 0; c < 3; c++) sum[i][c] = 1 << (RS_PRECISION_BITS - 1);
+            }
+#pragma clang loop vectorize(disable) interleave(disable)  // (taps two at a time cost more registers than the kernel has)
+            for (uint32_t x = 0; x < n; x++) {
+                const int32_t kx = k[x];
+#pragma unroll
+                for (uint32_t i = 0; i < RS_HROWS; i++) {
+                    const uint32_t d = pd[i][x], nk = 255u - (d >> 24);
+#pragma unroll
+                    for (uint32_t c = 0; c < 3; c++) sum[i][c] += (int32_t)cmyk_ink((d >> (8u * c)) & 255u, nk) * kx;
+                }
+            }
+#pragma unroll
+            for (uint32_t i = 0; i < RS_HROWS; i++) {
+                if (row0 + i >= nrows) continue;
+                uint8_t *o = lds + (row0 + i) * j.pitch + xx * 3u;
+#pragma unroll
+                for (uint32_t c = 0; c < 3; c++) {
+                    int32_t v = sum[i][c] >> RS_PRECISION_BITS;
+                    v = v < 0 ? 0 : (v > 255 ? 255 : v);
+                    o[c] = (uint8_t)v;
+                }
+            }
+        }
+    }
+    // the horizontal pass for a source of KIND channels that leaves three-channel rows (1: gray, 4: CMYK); 0: hpass
+    template <uint32_t KIND>
+    static __device__ __forceinline__ void hpass_of(const ResampleJob &j, const JP_GLOBAL int32_t *tab, uint32_t band, uint32_t chunk, uint32_t x0, uint32_t x1,
+                                                    uint32_t tid, uint8_t *lds) {
+        if (KIND == 1u) hpass_walk<1u>(j, tab, band, chunk, x0, x1, tid, lds);
+        else if (KIND == 4u) hpass_cmyk(j, tab, band, chunk, x0, x1, tid, lds);
+        else hpass(j, tab, band, chunk, x0, x1, tid, lds);
+    }
+
     // the share of source rows [c0, c1) (in LDS) in the four sums of destination dword q: where its bytes lie in one output row at a
     // multiple of four an aligned LDS dword per tap, else byte by byte
     static __device__ __forceinline__ void item_sum(const ResampleJob &j, const JP_GLOBAL int32_t *tab, uint32_t q, uint32_t a, uint32_t b, uint32_t c0,
@@ -327,6 +463,8 @@ struct RBand {
 #include <hip/hip_runtime.h>
 namespace jpgpu {
 // resample.hip: n_images jobs, their tables from d_tab; max_bands / lds_bytes over the jobs
-hipError_t launch_resample_band(const ResampleJob *d_jobs, const int32_t *d_tab, uint32_t n_images, uint32_t max_bands, uint32_t lds_bytes, hipStream_t stream);
+// (rgb: the instance whose horizontal pass converts jobs with src_nc != 0 — a batch created with JPGPU_BATCH_RGB_OUTPUT)
+hipError_t launch_resample_band(const ResampleJob *d_jobs, const int32_t *d_tab, uint32_t n_images, uint32_t max_bands, uint32_t lds_bytes, hipStream_t stream,
+                                bool rgb = false);
 }  // namespace jpgpu
 #endif

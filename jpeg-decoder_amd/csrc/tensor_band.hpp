@@ -13,6 +13,8 @@
 //     element by element, and a band stores its own elements only.
 //   * a flip mirrors the column READ from LDS; the stores stay where they are.
 //   * T sits in LDS behind the rows (at most 4 kB: 32 + 4 kB per workgroup, four workgroups per CU).
+//   * RGB output (JPGPU_BATCH_RGB_OUTPUT): nothing here knows of it — a gray or CMYK job arrives with nc = 3, its rows in
+//     LDS are three-channel (RBand::hpass_of) and T is the table of three channels.
 #pragma once
 #include <string.h>
 
@@ -341,8 +343,8 @@ struct TBand {
 #if defined(__HIP__) && !defined(JPGPU_HOST_EMULATION)
 namespace jpgpu {
 // resample.hip: n_images jobs, their resample tables from d_tab, the tensor table (4 x 256 elements of elem_bytes) from d_ttab;
-// max_bands / lds_bytes (the rows') over the jobs
+// max_bands / lds_bytes (the rows') over the jobs; rgb: the instances whose horizontal pass converts jobs with src_nc != 0
 hipError_t launch_resample_tensor(const TensorJob *d_jobs, const int32_t *d_tab, const void *d_ttab, uint32_t elem_bytes, uint32_t n_images, uint32_t max_bands,
-                                  uint32_t lds_bytes, hipStream_t stream);
+                                  uint32_t lds_bytes, hipStream_t stream, bool rgb = false);
 }  // namespace jpgpu
 #endif

@@ -76,7 +76,7 @@ class Pipeline:
 
     def decode(self, streams, download=True, dense=False, device_entropy=True, scale=None, color_transform=None, max_decoding_buffer_size=None,
                gather=False, host_light=None, input_pinned=False, progressive_on_host=False, windows=None, output_size=None,
-               tensor=None, flips=None):
+               tensor=None, flips=None, rgb=False):
         """-> list with, per stream, a numpy uint8 array of the decoded pixels (``Decoder.decode()``'s Vec<u8>) or the
         ``Error`` instance that stream produced.  download=False leaves the pixels in HBM (see ``device_pointer``); dense=True sends all
         64 coefficients of every block over PCIe instead of the compact form (same pixels, A/B switch); device_entropy=True
@@ -104,7 +104,10 @@ class Pipeline:
         stream's result is its resized pixels normalised and channel-first, an array of shape (nc, h, w) of the format's dtype (np.uint16
         bit patterns for bfloat16) written by the resample itself; ``download(i)`` / ``pixels_host(i)`` return the same.
         flips: None or one truth value per stream: that stream's columns mirrored (needs `tensor`, else FormatError and nothing is
-        decoded).  Fresh windows and flips for the same files keep the pipeline's sub-batches."""
+        decoded).  Fresh windows and flips for the same files keep the pipeline's sub-batches.
+        rgb: True (jpgpu_pipeline_set_rgb_output, set on every call; needs output_size, else FormatError and nothing is decoded): every
+        stream gives three channels — gray replicated, CMYK / YCCK converted as Pillow's ``convert("RGB")`` does, before the resample
+         — so arrays are (h * w * 3,) uint8 or (3, h, w); ``info(i)`` keeps the file's own components."""
         if isinstance(streams, PinnedFiles):
             bufs = None
             n = len(streams)
@@ -126,6 +129,7 @@ class Pipeline:
         check(st, L.jpgpu_pipeline_last_error(self._h) if st else b"")
         st = L.jpgpu_pipeline_set_tensor_output(self._h, None if fmt is None else C.byref(fmt))
         check(st, L.jpgpu_pipeline_last_error(self._h) if st else b"")
+        check(L.jpgpu_pipeline_set_rgb_output(self._h, 1 if rgb else 0), b"set_rgb_output")
         if bufs is None:
             ptrs = (C.c_void_p * max(n, 1))(*[streams.base + o for o in streams.offsets])
             lens = (C.c_size_t * max(n, 1))(*streams.lengths)
