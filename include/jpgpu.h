@@ -293,7 +293,8 @@ int jpgpu_batch_scan_ranges(jpgpu_batch *b, void *hip_stream, uint8_t *classes);
  * the host afterwards (upload, set_range_hint / set_range_class, scan_ranges) takes over again for that component. */
 int jpgpu_batch_classify_on_device(jpgpu_batch *b, void *hip_stream);
 /* Replace the quantization table given in the image descriptor (RowData.quantization_table of Worker::start,
- * src/worker/mod.rs:18-22): feeders learn it only while parsing the stream. Takes effect at the next decode.  If the table
+ * src/worker/mod.rs:18-22): feeders learn it only while parsing the stream. Takes effect at the next decode enqueued (a decode
+ * already enqueued keeps the old table: jpgpu_batch_decode).  If the table
  * differs from the one in place, the component's range class goes back to 0 (unknown: wrap-exact kernels) — the class of
  * coefficients uploaded earlier was computed with the old table; upload (or jpgpu_batch_set_range_class / scan_ranges) afterwards. */
 int jpgpu_batch_set_quantization_table(jpgpu_batch *b, uint32_t image, uint32_t comp, const uint16_t quantization_table[64]);
@@ -314,7 +315,22 @@ size_t jpgpu_compact_encode(const int16_t *coefficients, size_t n_blocks, const 
 int jpgpu_batch_upload_compact(jpgpu_batch *b, uint32_t image, uint32_t comp, const void *compact, size_t bytes,
                                int range_class, void *hip_stream);
 
-/* Enqueue the whole batch on `hip_stream` (a hipStream_t; NULL = the null stream). */
+/* Enqueue the whole batch on `hip_stream` (a hipStream_t; NULL = the null stream) and return: the decode is asynchronous.
+ *
+ * Batch calls on caller streams.  Every batch call that changes what a decode reads may be called as soon as jpgpu_batch_decode has
+ * returned, whatever kind of stream the decode is queued on (blocking or hipStreamNonBlocking) and however much work lies in front
+ * of it there: it affects only decodes enqueued LATER, the one already enqueued runs with the tables, classes, coefficients, arenas
+ * and flips the batch held when it was enqueued.  This covers jpgpu_batch_set_quantization_table ("the next decode" below means the
+ * next one enqueued), jpgpu_batch_set_range_hint, jpgpu_batch_set_range_class, jpgpu_batch_upload, jpgpu_batch_upload_compact,
+ * jpgpu_batch_bind, jpgpu_batch_set_flips, jpgpu_batch_scan_ranges, jpgpu_batch_classify_on_device, and the decode that follows any
+ * of them.  The library orders its own copies: where a table can only be rewritten by a blocking copy, the call that rewrites it
+ * (jpgpu_batch_upload; the next decode, scan or classification after the others) first waits on the host for the work the batch
+ * has enqueued — only when something did change, so a decode behind a decode gains no synchronisation.
+ * Out of contract (the caller orders these itself):
+ *   - decodes of one batch on two different streams without an event or a synchronisation between them;
+ *   - a jpgpu_batch_upload_compact on another stream than the one the next decode uses;
+ *   - the contents of the caller's own arenas under JPGPU_BATCH_EXTERNAL_BUFFERS (coefficients the caller writes into a bound arena,
+ *     pixels it reads from one): the library orders its tables, not the caller's kernels and copies. */
 int jpgpu_batch_decode(jpgpu_batch *b, void *hip_stream);
 int jpgpu_batch_synchronize(jpgpu_batch *b, void *hip_stream);
 /* HBM -> host download of one image's pixels. Blocking. */

@@ -49,6 +49,7 @@ static int batch_resample_tables(jpgpu_batch *b) {
         b->rs_max_bands = std::max(b->rs_max_bands, j.bands);
         b->rs_lds_bytes = std::max(b->rs_lds_bytes, j.lds_bytes);
     }
+    B_HIP(batch_wait_enqueued(b));  // (a decode still queued reads the tables)
     if (b->rs_tab.size() > b->rs_tab_cap) {
         B_HIP(hipDeviceSynchronize());
         B_HIP(grow_device(b->d_rs_tab, b->rs_tab_cap, b->rs_tab.size()));
@@ -100,6 +101,9 @@ static int batch_refresh_jobs(jpgpu_batch *b, hipStream_t stream = nullptr) {
     }
     if (!need_bind && !b->cls_dirty) return JPGPU_OK;
     if (!b->d_coef || !b->d_out) return set_err(b->err, JPGPU_ERR_FORMAT, "batch has no device buffers bound");
+    // The tables below go up by blocking copies on the null stream, which nothing orders behind a decode still queued on a non-blocking
+    // stream: that decode would read the next one's tables.  (The class table and the TensorJobs travel on `stream` itself.)
+    if (need_bind) B_HIP(batch_wait_enqueued(b));
     uint8_t *const pix = pix_base(b);
     const std::vector<size_t> &pix_off = pix_offsets(b);
     if (b->dev_classes) {
@@ -333,6 +337,10 @@ static int batch_create(int device, const jpgpu_image_desc *descs, const jpgpu_w
     for (FusedPlan &fp : b->fused) {
         rc = fused_alloc(fp, b->err);
         if (rc) return rc;
+        // no event per plan (a record per launch, a wait in fused_bind): b->enqueued stands behind the whole decode, and
+        // batch_refresh_jobs waits for it before anything is rebound
+        if (fp.launched) (void)hipEventDestroy(fp.launched);
+        fp.launched = nullptr;
     }
     B_HIP(hipMalloc((void **)&b->d_qt, (size_t)n_images * 4 * 64 * sizeof(uint16_t)));
     rc = batch_upload_qt(b);
@@ -343,6 +351,7 @@ static int batch_create(int device, const jpgpu_image_desc *descs, const jpgpu_w
     B_HIP(b->win.number_and_alloc(b->descs));
     B_HIP(hipEventCreate(&b->ev0));
     B_HIP(hipEventCreate(&b->ev1));
+    B_HIP(hipEventCreateWithFlags(&b->enqueued, hipEventDisableTiming));
     if (resized) return batch_resample_tables(b);
     return JPGPU_OK;
 }
@@ -401,6 +410,8 @@ void jpgpu_batch_destroy(jpgpu_batch *b) {
         if (b->d_qt) hipFree(b->d_qt);
         if (b->d_compact) hipFree(b->d_compact);
         if (b->d_expand_jobs) hipFree(b->d_expand_jobs);
+        if (b->h_expand_jobs) hipHostFree(b->h_expand_jobs);
+        if (b->expand_sent) hipEventDestroy(b->expand_sent);
         if (b->d_entropy) hipFree(b->d_entropy);
         if (b->h_entropy) hipHostFree(b->h_entropy);
         if (b->h_entropy_out) hipHostFree(b->h_entropy_out);
@@ -424,6 +435,7 @@ void jpgpu_batch_destroy(jpgpu_batch *b) {
         for (FusedPlan &fp : b->fused) fused_free(fp);
         if (b->ev0) hipEventDestroy(b->ev0);
         if (b->ev1) hipEventDestroy(b->ev1);
+        if (b->enqueued) hipEventDestroy(b->enqueued);
     }
     delete b;
 }
@@ -434,6 +446,7 @@ int jpgpu_batch_class_counts(jpgpu_batch *b, uint32_t counts[3]) {
     if (!b || !counts) return JPGPU_ERR_FORMAT;
     int rc = use_device(b->device, b->err);
     if (rc) return rc;
+    B_HIP(batch_wait_enqueued(b));  // (the refresh below sends on the null stream)
     rc = batch_refresh_jobs(b);
     if (rc) return rc;
     counts[0] = counts[1] = counts[2] = 0;
@@ -523,6 +536,7 @@ static int batch_scan_jobs(jpgpu_batch *b, uint32_t &n_jobs, uint32_t &max_block
                     memcpy(r.q, b->descs[i].quantization_tables[c], 128);
                     jobs.push_back(r);
                 }
+        B_HIP(batch_wait_enqueued(b));  // (a scan of jpgpu_batch_classify_on_device still queued reads the table)
         B_HIP(hipMemcpy(b->d_scan + jobs_off, jobs.data(), jobs.size() * sizeof(RangeJob), hipMemcpyHostToDevice));
         b->scan_jobs_valid = true;
     }
@@ -596,6 +610,7 @@ int jpgpu_batch_classify_on_device(jpgpu_batch *b, void *hip_stream) {
             b->sane[i * 4 + c] = 0;  // (the host does not know)
             batch_class_source(b, i * 4 + c, true);
         }
+    B_HIP(batch_mark_enqueued(b, s));  // (the scan reads its job table and the coefficient arena)
     return JPGPU_OK;
 }
 
@@ -633,6 +648,7 @@ int jpgpu_batch_upload(jpgpu_batch *b, uint32_t image, uint32_t comp, const int1
         std::lock_guard<std::mutex> g(b->compact_mutex);
         if (!b->compact_pending.empty()) b->compact_pending[(size_t)image * 4 + comp] = 0;
     }
+    B_HIP(batch_wait_enqueued(b));  // (a decode still queued reads the coefficients this copy replaces)
     B_HIP(hipMemcpy(b->d_coef + b->coef_off[image * 4 + comp], coefficients, len * sizeof(int16_t), hipMemcpyHostToDevice));
     return JPGPU_OK;
 }
@@ -676,6 +692,8 @@ int jpgpu::batch_upload_compact(jpgpu_batch *b, uint32_t image, uint32_t comp, c
                 }
             B_HIP(hipMalloc((void **)&b->d_compact, std::max<size_t>(off, 256)));
             B_HIP(hipMalloc((void **)&b->d_expand_jobs, n * 4 * sizeof(ExpandJob)));
+            B_HIP(hipHostMalloc((void **)&b->h_expand_jobs, n * 4 * sizeof(ExpandJob), hipHostMallocDefault));
+            B_HIP(hipEventCreateWithFlags(&b->expand_sent, hipEventDisableTiming));
         }
         // range_class < 0: the sender did not classify — expand_compact_kernel ranges the values while it expands them
         b->compact_pending[idx] = range_class >= 0 ? 1 : 2;
@@ -729,6 +747,7 @@ int jpgpu::batch_rewindow(jpgpu_batch *b, const jpgpu_window *windows) {
     uint8_t *&w_arena = b->rs_w ? b->d_pix : b->d_out;
     w_bytes = b->rs_w ? arena_layout(lens, b->pix_off, b->pix_len) : arena_layout(lens, b->out_off, b->out_len);
     b->jobs_dirty = true;  // (every job's output pointer, the fused plans' included)
+    B_HIP(batch_wait_enqueued(b));  // (idle by contract: the event has completed)
     if (w_bytes > w_cap) {
         B_HIP(hipDeviceSynchronize());
         B_HIP(grow_device(w_arena, w_cap, w_bytes, arena_headroom(w_bytes, arena_layout(b->out_full_len))));
@@ -792,7 +811,12 @@ static int batch_expand_pending(jpgpu_batch *b, hipStream_t s) {
     }
     if (jobs.empty()) return JPGPU_OK;
     for (uint32_t img : stat_fresh) B_HIP(hipMemsetAsync(b->d_stats + (size_t)img * RS_WORDS, 0, RS_WORDS * sizeof(uint32_t), s));
-    B_HIP(hipMemcpy(b->d_expand_jobs, jobs.data(), jobs.size() * sizeof(ExpandJob), hipMemcpyHostToDevice));
+    // The jobs follow the expansion before them on its own stream (a blocking copy on the null stream could overtake it on a non-blocking
+    // stream, and would hold every decode of a loader up); the mirror is free once its last copy has left it.
+    B_HIP(hipEventSynchronize(b->expand_sent));
+    memcpy(b->h_expand_jobs, jobs.data(), jobs.size() * sizeof(ExpandJob));
+    B_HIP(hipMemcpyAsync(b->d_expand_jobs, b->h_expand_jobs, jobs.size() * sizeof(ExpandJob), hipMemcpyHostToDevice, s));
+    B_HIP(hipEventRecord(b->expand_sent, s));
     B_HIP(launch_expand_compact(b->d_expand_jobs, (uint32_t)jobs.size(), max_blocks, s));
     return JPGPU_OK;
 }
@@ -846,6 +870,7 @@ int jpgpu_batch_decode(jpgpu_batch *b, void *hip_stream) {
     else if (b->rs_w)  // (an output size: every image's pixels, wherever the launches above left them in the intermediate arena)
         B_HIP(launch_resample_band(b->d_rs_jobs, b->d_rs_tab, (uint32_t)b->descs.size(), b->rs_max_bands, b->rs_lds_bytes, s, (b->flags & JPGPU_BATCH_RGB_OUTPUT) != 0));
     if (b->phase_events_valid) B_HIP(hipEventRecord(b->ev_phase[5], s));
+    B_HIP(batch_mark_enqueued(b, s));
     return JPGPU_OK;
 }
 

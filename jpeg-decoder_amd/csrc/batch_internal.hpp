@@ -142,12 +142,20 @@ struct jpgpu_batch {
     hipEvent_t tn_sent = nullptr;      // behind the last copy out of the mirror
     void *d_tn_table = nullptr;        // 4 x 256 elements
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
+    // Behind the last work enqueued on a caller's stream that reads the batch's tables or its coefficient arena (every decode,
+    // jpgpu_batch_classify_on_device).  That stream may be a non-blocking one, which a blocking copy on the null stream does not order
+    // against: every host-side rewrite of something such work reads waits for the event first (batch_wait_enqueued) — only then, so a
+    // decode after a decode with nothing changed never waits.
+    hipEvent_t enqueued = nullptr;
+    bool enqueue_pending = false;
     // compact transport (compact.hpp): staging area in HBM, allocated at the first jpgpu_batch_upload_compact
     std::mutex compact_mutex;
     uint8_t *d_compact = nullptr;
     std::vector<size_t> compact_off;      // [image*4 + comp]
     std::vector<uint8_t> compact_pending; // [image*4 + comp]: uploaded, to be expanded by the next decode
     ExpandJob *d_expand_jobs = nullptr;
+    ExpandJob *h_expand_jobs = nullptr;   // pinned mirror: the jobs travel on the decode's stream, behind the expansion before them
+    hipEvent_t expand_sent = nullptr;     // behind the last copy out of the mirror
     bool any_compact_pending = false;
     // device entropy decoding (huff.hip): one pinned + one device staging block, grown on demand
     uint8_t *h_entropy = nullptr, *d_entropy = nullptr;
@@ -199,6 +207,18 @@ struct jpgpu_batch {
         hipError_t _e = (call);                                                                         \
         if (_e != hipSuccess) return set_err(b->err, JPGPU_ERR_IO, "%s: %s", #call, hipGetErrorString(_e)); \
     } while (0)
+
+// before a blocking rewrite of anything enqueued work reads (see jpgpu_batch::enqueued); free when nothing was enqueued since the last wait
+static hipError_t batch_wait_enqueued(jpgpu_batch *b) {
+    if (!b->enqueue_pending) return hipSuccess;
+    b->enqueue_pending = false;
+    return hipEventSynchronize(b->enqueued);
+}
+static hipError_t batch_mark_enqueued(jpgpu_batch *b, hipStream_t s) {
+    const hipError_t e = hipEventRecord(b->enqueued, s);
+    if (e == hipSuccess) b->enqueue_pending = true;
+    return e;
+}
 
 // where the pixel kernels write: the output arena, or the intermediate one of a batch with an output size
 static uint8_t *pix_base(const jpgpu_batch *b) { return b->rs_w ? b->d_pix : b->d_out; }
@@ -290,7 +310,7 @@ int BandGroup<Geom>::fill_jobs(jpgpu_batch *b, uint8_t *pix, const std::vector<s
         if (rc) return rc;
         image_jobs.push_back(ij);
     }
-    if (!plane_jobs.empty()) {
+    if (!plane_jobs.empty()) {  // (batch_refresh_jobs has waited for the decodes enqueued: batch_wait_enqueued)
         B_HIP(hipMemcpy(d_plane_jobs, plane_jobs.data(), plane_jobs.size() * sizeof(PlaneJob), hipMemcpyHostToDevice));
         B_HIP(hipMemcpy(d_image_jobs, image_jobs.data(), image_jobs.size() * sizeof(ImageJob), hipMemcpyHostToDevice));
     }

@@ -9,6 +9,7 @@ import numpy as np
 import pytest
 
 import oracle as O
+import stream_harness  # (at collection time: it imports torch before any test loads libjpgpu.so)
 import synth
 
 pytestmark = pytest.mark.gpu
@@ -336,24 +337,48 @@ def _describe(op):
     return op[0]
 
 
-def _run_ops(layout, ops, label):
+def _run_ops(layout, ops, label, stream=None, deferred=False):
     """Applies `ops` to a Batch and to the host model; after every decode, every image must equal the oracle's decode of the model,
-    and on the fused paths the class split must not promise more than the exact classes allow."""
+    and on the fused paths the class split must not promise more than the exact classes allow.
+
+    stream: a tests/stream_harness.py StreamHarness whose stream every call that takes one runs on (None: the null stream).
+    deferred: the host does not wait after a decode — ballast in front of it and a snapshot of the output arena behind it, both on the
+    stream, replace synchronize() and download(); the snapshots are compared with the model's state at their decode after one host
+    wait at the end, the class split once, after the last decode.  Every mutating operation that directly follows a decode (nothing
+    that drains the stream in between: a scan, the wrapper's compact upload, a dense upload, a classification) must find that decode
+    pending; the count of those that did is returned."""
     ocs = [O.make_components(w, h, samp)[0] for (w, h, samp, _ct) in layout]
     assert ops[0][0] == "create"
+    assert stream is not None or not deferred
+    sh = None if stream is None else stream.handle
     qts = [list(q) for q in ops[0][1]]
     coefs = [[np.zeros(c.block_w * c.block_h * 64, np.int16) for c in oc] for oc in ocs]
     b = J.Batch([J.image_desc(list(_to_j(oc)), qts[i], w, h, ct) for i, (oc, (w, h, _s, ct)) in enumerate(zip(ocs, layout))])
     log = ["create"]
+
+    def split_check(at):
+        if b.path != "generic":
+            exact = [_exact_class(qts[i], coefs[i]) for i in range(len(ocs))]
+            counts = b.class_counts()
+            assert counts[2] <= sum(e == 3 for e in exact) and counts[1] + counts[2] <= sum(e >= 1 for e in exact), (
+                f"{label}: class split {counts} promises more than the exact classes {exact} after operation {at}:\n  " + "\n  ".join(log))
+
+    snaps = stream.buffers(sum(op[0] == "decode" for op in ops), b.out_arena_bytes()) if deferred else None
+    taken = []     # deferred: per decode (operation number, the model's tables and coefficients then)
+    behind = None  # deferred: the event behind the last decode while nothing has drained the stream since
     try:
         for op in ops[1:]:
             log.append(_describe(op))
+            if deferred and behind is not None and op[0] != "decode":
+                stream.expect_pending(behind, f"operation {len(log) - 1} ({log[-1]}) of {label}")
+                if op[0] not in ("qt", "hint"):  # (those two change host state only)
+                    behind = None
             if op[0] == "up":
                 _, i, c, cf, mode = op[:5]
                 if mode == "dense":
                     b.upload(i, c, cf)
                 else:
-                    b.upload_compact(i, c, cf, classify=(mode == "compact"))
+                    b.upload_compact(i, c, cf, stream=sh, classify=(mode == "compact"))
                 coefs[i][c] = cf
             elif op[0] == "qt":
                 _, i, c, q = op[:4]
@@ -362,23 +387,42 @@ def _run_ops(layout, ops, label):
             elif op[0] == "hint":
                 b.set_range_hint(op[1], op[2])
             elif op[0] == "scan":
-                b.scan_ranges()
+                b.scan_ranges(sh)
             elif op[0] == "classify":
-                b.classify_on_device()
+                b.classify_on_device(sh)
+            elif deferred:
+                stream.ballast()
+                b.decode(sh)
+                behind = stream.mark()
+                stream.snapshot(snaps[len(taken)], b.out_arena(), b.out_arena_bytes())
+                taken.append((len(log) - 1, [list(q) for q in qts], [list(c) for c in coefs]))
             else:
-                b.decode()
-                b.synchronize()
+                b.decode(sh)
+                b.synchronize(sh)
                 bad = []
                 for i, (oc, (w, h, _s, ct)) in enumerate(zip(ocs, layout)):
                     if not np.array_equal(b.download(i), O.pixels_from_coefficients(oc, qts[i], coefs[i], w, h, ct.upper())):
                         bad.append(i)
                 if bad:
                     pytest.fail(f"{label}: images {bad} differ from the model after operation {len(log) - 1}:\n  " + "\n  ".join(log))
-                if b.path != "generic":
-                    exact = [_exact_class(qts[i], coefs[i]) for i in range(len(ocs))]
-                    counts = b.class_counts()
-                    assert counts[2] <= sum(e == 3 for e in exact) and counts[1] + counts[2] <= sum(e >= 1 for e in exact), (
-                        f"{label}: class split {counts} promises more than the exact classes {exact} after operation {len(log) - 1}:\n  " + "\n  ".join(log))
+                split_check(len(log) - 1)
+        if deferred:
+            stream.finish()
+            got = snaps.cpu().numpy()
+            wrong = []
+            for k, (at, q_then, c_then) in enumerate(taken):
+                bad = []
+                for i, (oc, (w, h, _s, ct)) in enumerate(zip(ocs, layout)):
+                    want = O.pixels_from_coefficients(oc, q_then[i], c_then[i], w, h, ct.upper())
+                    off = b.out_offset(i)
+                    if not np.array_equal(got[k][off: off + want.size], want):
+                        bad.append(i)
+                if bad:
+                    wrong.append(f"images {bad} after operation {at}")
+            if wrong:
+                pytest.fail(f"{label}: snapshots differ from the model: " + "; ".join(wrong) + ":\n  " + "\n  ".join(log))
+            split_check(len(log) - 1)
+            return stream.checked
     finally:
         b.close()
 
@@ -389,6 +433,22 @@ def test_random_batch_operation_sequences(layout, run):
     """On failure the message holds the seed and the operation log: shrink it by hand into a named test like the two below."""
     seed = 7000 + 10 * run + sorted(LAYOUTS).index(layout)
     _run_ops(LAYOUTS[layout], _random_ops(LAYOUTS[layout], seed), f"layout {layout}, seed {seed}")
+
+
+@pytest.mark.parametrize("layout", sorted(LAYOUTS))
+def test_random_batch_operation_sequences_on_a_nonblocking_stream(layout):
+    """The lists of run 0 above with every call on a hipStreamNonBlocking stream and the host never waiting after a decode: each
+    decode is still queued behind its ballast when the operations after it change tables, classes and coefficients."""
+    seed = 7000 + sorted(LAYOUTS).index(layout)
+    ops = _random_ops(LAYOUTS[layout], seed)
+    h = stream_harness.StreamHarness("nonblocking")
+    try:
+        held = _run_ops(LAYOUTS[layout], ops, f"layout {layout}, seed {seed}, non-blocking stream", stream=h, deferred=True)
+    finally:
+        h.close()
+    follow = sum(1 for prev, op in zip(ops[1:], ops[2:]) if prev[0] == "decode" and op[0] != "decode")
+    print(f"layout {layout}: {held} mutating operations found the decode in front of them pending ({follow} directly behind a decode)")
+    assert held >= follow > 0, (held, follow)
 
 
 def _small_and_wrapping(layout, seed):
