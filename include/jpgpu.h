@@ -244,6 +244,57 @@ int jpgpu_batch_set_flips(jpgpu_batch *b, const uint8_t *flips);
 /* The table T of a format for images of `nc` channels (1..4) as the batch computes it (pure host function, no device needed): `table`
  * receives nc x 256 elements of the format's dtype (bf16 / f16 as their 16-bit patterns).  A refused format: JPGPU_ERR_FORMAT. */
 int jpgpu_tensor_table(const jpgpu_tensor_format *format, uint32_t nc, void *table);
+/* ---- Resize, then crop or pad: a placement per image in the fixed output size ------------------------------------------------------
+ * jpgpu_batch_create_resized / _create_tensor (`format` NULL: u8) with a placement per image: the image's source is resampled to a
+ * size of its own, rw x rh, and laid with its top-left pixel at (x, y) into the out_w x out_h output.  What falls outside is cropped,
+ * what the image does not cover is `fill`.  With R the resample of the image's source to rw x rh, the output of image i is
+ *     out(Y, X, c) = R(Y - y, X - x, c)   if 0 <= X - x < rw and 0 <= Y - y < rh
+ *                  = fill[c]              otherwise
+ *   - the source is the image's window, or its whole output, in the grid after the DCT scale — the source of the fixed output size,
+ *     after the RGB conversion when JPGPU_BATCH_RGB_OUTPUT is set;
+ *   - R follows rules 1-6 of jpgpu_batch_create_resized with out_size = rw / rh, the horizontal pass first;
+ *   - `fill` is four bytes per batch in the output's channel order (NULL: zeros);
+ *   - the Pillow equivalent is canvas = Image.new(mode, (out_w, out_h), fill); canvas.paste(src.resize((rw, rh), BILINEAR), (x, y));
+ *   - with a tensor format the element is T[c][out(r, flip ? out_w - 1 - x : x, c)]: a filled element is T[c][fill[c]] — what Pad(fill)
+ *     in front of Normalize gives — and the flip mirrors the finished canvas, padding included;
+ *   - the known difference from Pillow stays as documented: sources with H > 100 W and rh < H.
+ * rw == 0 or rh == 0 means "none" = (out_w, out_h, 0, 0).  Every output pixel of the two-pass resample depends on its own row and column
+ * of the tables only: the visible part is computed from the sub-range of the tables the output covers
+ * (jpgpu_resample_coefficients_range), nothing outside it.  Output sizes, offsets, the arena, jpgpu_batch_download,
+ * JPGPU_BATCH_EXTERNAL_BUFFERS, jpgpu_batch_set_flips and caller streams are those of the fixed output size.  jpgpu_batch_path gains
+ * "+place" before "+resize" exactly when some image has a placement other than (out_w, out_h, 0, 0); `placements` NULL, or no such
+ * image, IS jpgpu_batch_create_resized / _create_tensor: the same kernels and path.
+ * Refusals: a placement must show at least one pixel — x < out_w, x + rw > 0, y < out_h, y + rh > 0 — else JPGPU_ERR_FORMAT; planar
+ * ColorTransform None images stay JPGPU_ERR_UNSUPPORTED. */
+typedef struct jpgpu_placement {
+    uint16_t rw, rh; /* the size the image's source is resampled to, 1..65535 each; rw == 0 or rh == 0: "none" = (out_w, out_h, 0, 0) */
+    int32_t x, y;    /* where that resampled image's top-left pixel lies in the out_w x out_h output; negative: cropped */
+} jpgpu_placement;
+int jpgpu_batch_create_placed(int device, const jpgpu_image_desc *descs, const jpgpu_window *windows, const jpgpu_placement *placements,
+                              const uint8_t *fill, uint16_t out_w, uint16_t out_h, const jpgpu_tensor_format *format, uint32_t n_images,
+                              uint32_t flags, jpgpu_batch **out);
+/* Entries [first, first + count) of the tables jpgpu_resample_coefficients(in_size, out_size, ...) gives (pure host function): bounds
+ * receives 2 * count, coefs count * ksize words, ksize = jpgpu_resample_coefficients' for (in_size, out_size).  Computed per entry
+ * from the same statements: an axis of 65535 entries is never tabulated whole.  first + count > out_size: JPGPU_ERR_FORMAT. */
+int jpgpu_resample_coefficients_range(uint32_t in_size, uint32_t out_size, uint32_t first, uint32_t count, int32_t *bounds, int32_t *coefs,
+                                      uint32_t *ksize);
+/* The placement of a source of src_w x src_h in an output of out_w x out_h under a rule (pure host function):
+ *   JPGPU_FIT_STRETCH: (out_w, out_h, 0, 0).
+ *   JPGPU_FIT_SHORTER_SIDE_CROP — torchvision's Resize(size) then CenterCrop((out_h, out_w)): w <= h: rw = size, rh = size * h / w;
+ *     else rh = size, rw = size * w / h (64-bit integer division).  Per axis, d = r - out: d >= 0: the offset is -round_half_even(d / 2);
+ *     d < 0: the offset is (out - r) / 2 rounded down.  A side above 65535: JPGPU_ERR_FORMAT.
+ *   JPGPU_FIT_LETTERBOX, in IEEE double, one operation per statement: r = min(out_w / w, out_h / h); rw = max(1, rint(w r)),
+ *     rh = max(1, rint(h r)), each capped at the output's; x = (int)rint((out_w - rw) / 2.0 - 0.1), y likewise (rint: to nearest even).
+ * `fill` is what the caller passes on to jpgpu_batch_create_placed.  An unknown mode, reserved != 0, a zero size (mode 1: `size` too):
+ * JPGPU_ERR_FORMAT. */
+enum { JPGPU_FIT_STRETCH = 0, JPGPU_FIT_SHORTER_SIDE_CROP = 1, JPGPU_FIT_LETTERBOX = 2 };
+typedef struct jpgpu_fit {
+    uint32_t mode; /* JPGPU_FIT_* */
+    uint32_t size; /* JPGPU_FIT_SHORTER_SIDE_CROP: what the shorter side is resampled to */
+    uint8_t fill[4];
+    uint32_t reserved; /* 0 */
+} jpgpu_fit;
+int jpgpu_fit_placement(const jpgpu_fit *fit, uint32_t src_w, uint32_t src_h, uint32_t out_w, uint32_t out_h, jpgpu_placement *out);
 void jpgpu_batch_destroy(jpgpu_batch *b);
 const char *jpgpu_batch_last_error(const jpgpu_batch *b);
 

@@ -248,6 +248,19 @@ int jpgpu_pipeline_set_tensor_output(jpgpu_pipeline *p, const jpgpu_tensor_forma
  * hold / count the three-channel bytes; jpgpu_pipeline_image_info keeps reporting the file's own components and pixel format.
  * Switching it on or off between calls creates the kept sub-batches anew, as a changed output size does. */
 int jpgpu_pipeline_set_rgb_output(jpgpu_pipeline *p, int on);
+/* A placement rule for every image of the calls that follow (sticky, like the output size): each image's source — its window's
+ * size, else its output's, after jpgpu_pipeline_set_scale — is placed in the output size by jpgpu_fit_placement(fit, ...) of its own
+ * size, and its sub-batch is created with jpgpu_batch_create_placed (jpgpu.h: resampled to a size of its own, cropped, filled with
+ * fit->fill).  JPGPU_FIT_SHORTER_SIDE_CROP with size 256 and an output size of 224 x 224 is torchvision's Resize(256) + CenterCrop(224);
+ * JPGPU_FIT_LETTERBOX the aspect-preserving fit with constant padding.  NULL or JPGPU_FIT_STRETCH: off — the routes, launches and bytes of
+ * the output size alone.  A fit needs an output size: without one the next decode fails whole with JPGPU_ERR_FORMAT before anything is
+ * decoded.  An image whose rule is refused (a resampled side above 65535) fails alone with JPGPU_ERR_FORMAT.  A changed fit creates the
+ * kept sub-batches anew; fresh windows at the same fit are re-placed in place with them.  Composes with the scale, the tensor format,
+ * flips, RGB output and windows.  An unknown mode, reserved != 0 or size 0 with mode 1: JPGPU_ERR_FORMAT, nothing changes. */
+int jpgpu_pipeline_set_fit(jpgpu_pipeline *p, const jpgpu_fit *fit);
+/* The placement image `image` of the last call was decoded with: jpgpu_fit_placement of its source size, (out_w, out_h, 0, 0) without a
+ * fit.  JPGPU_ERR_FORMAT without an output size, for an image without a frame, or one whose window or rule was refused. */
+int jpgpu_pipeline_image_placement(const jpgpu_pipeline *p, uint32_t image, jpgpu_placement *out);
 /* Decoder::set_color_transform (src/decoder.rs:158-161) for every image of the calls that follow: one of the JPGPU_CT_* values of
  * jpgpu.h instead of what determine_color_transform finds per image; a negative value: per image again (the default). */
 int jpgpu_pipeline_set_color_transform(jpgpu_pipeline *p, int color_transform);

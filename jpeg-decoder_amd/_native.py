@@ -78,6 +78,19 @@ class TensorFormatStruct(C.Structure):
     _fields_ = [("dtype", C.c_uint32), ("reserved", C.c_uint32), ("mean", C.c_float * 4), ("std", C.c_float * 4)]
 
 
+class Placement(C.Structure):
+    """jpgpu_placement: the size the source is resampled to and where its top-left pixel lies in the output; rw == 0 or rh == 0 = none."""
+    _fields_ = [("rw", C.c_uint16), ("rh", C.c_uint16), ("x", C.c_int32), ("y", C.c_int32)]
+
+
+FIT_STRETCH, FIT_SHORTER_SIDE_CROP, FIT_LETTERBOX = 0, 1, 2
+
+
+class FitStruct(C.Structure):
+    """jpgpu_fit: mode (FIT_*), size (shorter side of FIT_SHORTER_SIDE_CROP), fill[4], reserved = 0."""
+    _fields_ = [("mode", C.c_uint32), ("size", C.c_uint32), ("fill", C.c_uint8 * 4), ("reserved", C.c_uint32)]
+
+
 class PipelineTimings(C.Structure):
     _fields_ = [(n, C.c_double) for n in ("headers_ms", "setup_ms", "entropy_and_upload_ms", "kernels_ms", "download_ms", "total_ms")] + \
                [("threads", C.c_uint32), ("images_ok", C.c_uint32), ("jpeg_bytes", C.c_uint64), ("coefficient_bytes", C.c_uint64),
@@ -135,6 +148,10 @@ _PROTOS = {
                                              C.POINTER(C.c_void_p)]),
     "jpgpu_batch_create_tensor": (C.c_int, [C.c_int, C.POINTER(ImageDesc), C.POINTER(Window), C.c_uint16, C.c_uint16, C.POINTER(TensorFormatStruct), C.c_uint32,
                                             C.c_uint32, C.POINTER(C.c_void_p)]),
+    "jpgpu_batch_create_placed": (C.c_int, [C.c_int, C.POINTER(ImageDesc), C.POINTER(Window), C.POINTER(Placement), C.c_void_p, C.c_uint16, C.c_uint16,
+                                            C.POINTER(TensorFormatStruct), C.c_uint32, C.c_uint32, C.POINTER(C.c_void_p)]),
+    "jpgpu_resample_coefficients_range": (C.c_int, [C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.POINTER(C.c_uint32)]),
+    "jpgpu_fit_placement": (C.c_int, [C.POINTER(FitStruct), C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(Placement)]),
     "jpgpu_batch_set_flips": (C.c_int, [C.c_void_p, C.c_void_p]),
     "jpgpu_tensor_table": (C.c_int, [C.POINTER(TensorFormatStruct), C.c_uint32, C.c_void_p]),
     "jpgpu_resample_coefficients": (C.c_int, [C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.POINTER(C.c_uint32)]),
@@ -208,6 +225,8 @@ _PROTOS = {
     "jpgpu_pipeline_set_output_size": (C.c_int, [C.c_void_p, C.c_uint16, C.c_uint16]),
     "jpgpu_pipeline_set_tensor_output": (C.c_int, [C.c_void_p, C.POINTER(TensorFormatStruct)]),
     "jpgpu_pipeline_set_rgb_output": (C.c_int, [C.c_void_p, C.c_int]),
+    "jpgpu_pipeline_set_fit": (C.c_int, [C.c_void_p, C.POINTER(FitStruct)]),
+    "jpgpu_pipeline_image_placement": (C.c_int, [C.c_void_p, C.c_uint32, C.POINTER(Placement)]),
     "jpgpu_pipeline_set_color_transform": (C.c_int, [C.c_void_p, C.c_int]),
     "jpgpu_pipeline_set_max_decoding_buffer_size": (C.c_int, [C.c_void_p, C.c_size_t]),
     "jpgpu_pipeline_download": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]),

@@ -93,6 +93,64 @@ class TensorFormat:
         return f"TensorFormat({self.dtype!r}, mean={self.mean}, std={self.std})"
 
 
+class Fit:
+    """A placement rule (jpgpu_fit): how a source of its own size is laid into the fixed output size.  ``mode`` "stretch" (the whole
+    output, today's behaviour), "shorter_side_crop" (torchvision's ``Resize(size)`` then ``CenterCrop``: the evaluation transform) or
+    "letterbox" (the aspect-preserving fit with constant padding).  ``fill``: up to four bytes in the output's channel order."""
+    MODES = {"stretch": N.FIT_STRETCH, "shorter_side_crop": N.FIT_SHORTER_SIDE_CROP, "letterbox": N.FIT_LETTERBOX}
+
+    def __init__(self, mode="stretch", size=0, fill=(0, 0, 0, 0)):
+        if mode not in self.MODES:
+            raise ValueError(f"fit mode {mode!r}: one of {sorted(self.MODES)}")
+        self.mode, self.size, self.fill = mode, int(size), fill_tuple(fill)
+
+    def struct(self):
+        s = N.FitStruct()
+        s.mode, s.size, s.reserved = self.MODES[self.mode], self.size, 0
+        for c in range(4):
+            s.fill[c] = self.fill[c]
+        return s
+
+    def __repr__(self):
+        return f"Fit({self.mode!r}, size={self.size}, fill={self.fill})"
+
+
+def fill_tuple(fill):
+    """Up to four fill bytes -> a tuple of four (missing channels: 0)."""
+    fill = [int(v) for v in (fill if fill is not None else ())]
+    if len(fill) > 4 or any(v < 0 or v > 255 for v in fill):
+        raise ValueError(f"fill {fill!r}: at most four bytes")
+    return tuple(fill + [0] * (4 - len(fill)))
+
+
+def fit_placement(fit, src_size, output_size):
+    """jpgpu_fit_placement: the placement (rw, rh, x, y) of a source of ``src_size`` = (w, h) in ``output_size`` = (w, h) under ``fit``
+    (a Fit, or a raw N.FitStruct).  A refused rule (a side above 65535, an unknown mode) raises FormatError."""
+    s = fit.struct() if isinstance(fit, Fit) else fit
+    pl = N.Placement()
+    check(N.lib().jpgpu_fit_placement(C.byref(s), int(src_size[0]), int(src_size[1]), int(output_size[0]), int(output_size[1]), C.byref(pl)),
+          b"jpgpu_fit_placement: refused")
+    return (pl.rw, pl.rh, pl.x, pl.y)
+
+
+def placement_structs(placements, n):
+    """`placements`: None or a list with (rw, rh, x, y) or None per image -> (ctypes array or None)."""
+    if placements is None:
+        return None
+    placements = list(placements)
+    if len(placements) != n:
+        raise ValueError(f"{len(placements)} placements for {n} images")
+    arr = (N.Placement * max(n, 1))()
+    for i, pl in enumerate(placements):
+        if pl is None:
+            continue
+        rw, rh, x, y = (int(v) for v in pl)
+        if not (0 <= rw <= 65535 and 0 <= rh <= 65535 and -2 ** 31 <= x < 2 ** 31 and -2 ** 31 <= y < 2 ** 31):
+            raise ValueError(f"placement {pl!r}")
+        arr[i].rw, arr[i].rh, arr[i].x, arr[i].y = rw, rh, x, y
+    return arr
+
+
 def flip_bytes(flips, n):
     """`flips`: None or one truth value per image -> (ctypes array of n bytes or None)."""
     if flips is None:
@@ -128,9 +186,16 @@ class Batch:
 
     rgb: True adds BATCH_RGB_OUTPUT (needs an output_size, else UnsupportedError): every image gives three channels — gray replicated,
     CMYK / YCCK through Pillow's integer cmyk2rgb, before the resample (``Image.convert("RGB")`` then crop and resize)
-    — so arrays are (h * w * 3,) uint8 or (3, h, w) whatever the files hold; `path` gains "+rgb" before "+resize"."""
+    — so arrays are (h * w * 3,) uint8 or (3, h, w) whatever the files hold; `path` gains "+rgb" before "+resize".
 
-    def __init__(self, descs, device=0, flags=N.BATCH_DEFAULT, windows=None, output_size=None, tensor=None, rgb=False):
+    placements: None, or a list with (rw, rh, x, y) or None per image (jpgpu_batch_create_placed; needs an output_size).  The image's
+    source is resampled to rw x rh — a size of its own — and laid with its top-left pixel at (x, y) in the output: what falls outside
+    is cropped, what it does not cover is ``fill`` (up to four bytes, the output's channel order).  Pillow's
+    ``canvas = Image.new(mode, (w, h), fill); canvas.paste(src.resize((rw, rh), BILINEAR), (x, y))``; with a tensor a filled element is
+    ``T[c][fill[c]]`` and a flip mirrors the finished canvas.  `path` gains "+place" before "+resize" when some image
+    has a placement other than (w, h, 0, 0); one that shows no pixel is a FormatError, a list of another length a ValueError."""
+
+    def __init__(self, descs, device=0, flags=N.BATCH_DEFAULT, windows=None, output_size=None, tensor=None, rgb=False, placements=None, fill=None):
         self._h = C.c_void_p()
         arr = (N.ImageDesc * len(descs))(*descs)
         wins = window_structs(windows, len(descs))
@@ -139,7 +204,14 @@ class Batch:
         self.rgb = bool(rgb) or bool(flags & N.BATCH_RGB_OUTPUT)
         if rgb:
             flags |= N.BATCH_RGB_OUTPUT
-        if tensor is not None:
+        pls = placement_structs(placements, len(descs))
+        self.fill = fill_tuple(fill)
+        if pls is not None:
+            w, h = self.output_size if self.output_size is not None else (0, 0)
+            fmt = tensor.struct() if tensor is not None else None
+            st = N.lib().jpgpu_batch_create_placed(device, arr, wins, pls, (C.c_uint8 * 4)(*self.fill), w, h, C.byref(fmt) if fmt is not None else None,
+                                                   len(descs), flags, C.byref(self._h))
+        elif tensor is not None:
             w, h = self.output_size if self.output_size is not None else (0, 0)
             fmt = tensor.struct()
             st = N.lib().jpgpu_batch_create_tensor(device, arr, wins, w, h, C.byref(fmt), len(descs), flags, C.byref(self._h))

@@ -7,6 +7,7 @@
 // Images of a fusable kind (4:2:0 YCbCr, 4:4:4 YCbCr / RGB, gray; any size) are grouped per kind and run the fused
 // kernels (fused.hip), one launch group per kind; everything else runs the generic two-kernel path (kernels.hip)
 // through device job tables.  jpgpu_batch_path names the kernels: "fused420", ..., "generic", or "mixed".
+#include <array>
 #include <map>
 
 #include "batch_internal.hpp"
@@ -32,6 +33,22 @@ static int batch_resample_tables(jpgpu_batch *b) {
         seen[key] = {bo, ko};
         return true;
     };
+    // a placed batch: entries [first, first + count) of the axis (in, out) — the visible range, nothing else is tabulated
+    std::map<std::array<uint32_t, 4>, std::pair<uint32_t, uint32_t>> seen_range;
+    auto axis_range = [&](uint32_t in, uint32_t out, uint32_t first, uint32_t count, uint32_t &bo, uint32_t &ko, uint32_t &ks) {
+        ks = resample_ksize(in, out);
+        const std::array<uint32_t, 4> key = {in, out, first, count};
+        auto it = seen_range.find(key);
+        if (it != seen_range.end()) return bo = it->second.first, ko = it->second.second, true;
+        const size_t base = b->rs_tab.size(), end = base + 2u * (size_t)count + (size_t)count * ks;
+        if (end > 0xffffffffull) return false;
+        b->rs_tab.resize(end);
+        bo = (uint32_t)base, ko = (uint32_t)(base + 2u * count);
+        resample_coefficients_range(in, out, first, count, b->rs_tab.data() + bo, b->rs_tab.data() + ko, ks);
+        seen_range[key] = {bo, ko};
+        return true;
+    };
+    if (b->placed) b->rs_places.assign(n, Place{});
     size_t k = 0;
     for (uint32_t i = 0; i < n; i++) {
         const jpgpu_image_desc &d = b->descs[i];
@@ -40,13 +57,29 @@ static int batch_resample_tables(jpgpu_batch *b) {
         if (k < b->win.ids.size() && b->win.ids[k] == i) j.in_w = b->win.geoms[k].ww, j.in_h = b->win.geoms[k].wh, k++;
         j.nc = d.ncomp, j.out_w = b->rs_w, j.out_h = b->rs_h;
         if (b->flags & JPGPU_BATCH_RGB_OUTPUT) j.nc = 3u, j.src_nc = d.ncomp == 3u ? 0u : d.ncomp;  // (gray / CMYK: converted by the horizontal pass)
+        if (b->placed) {  // (the job of the visible rectangle)
+            const jpgpu_placement &pl = b->pl[i];
+            Place &p = b->rs_places[i];
+            uint32_t fx = 0, fy = 0;
+            if (!placed_axis(pl.rw, pl.x, b->rs_w, fx, j.out_w, p.vx) || !placed_axis(pl.rh, pl.y, b->rs_h, fy, j.out_h, p.vy))
+                return set_err(b->err, JPGPU_ERR_FORMAT, "image %u: the placement shows no pixel", i);
+            p.cw = b->rs_w, p.ch = b->rs_h, p.fill = b->pl_fill;
+            if (!axis_range(j.in_w, pl.rw, fx, j.out_w, j.hb, j.hk, j.hks) || !axis_range(j.in_h, pl.rh, fy, j.out_h, j.vb, j.vk, j.vks))
+                return set_err(b->err, JPGPU_ERR_UNSUPPORTED, "image %u: resample tables of the batch exceed 2^32 words", i);
+            continue;
+        }
         if (!axis(j.in_w, j.out_w, j.hb, j.hk, j.hks) || !axis(j.in_h, j.out_h, j.vb, j.vk, j.vks))
             return set_err(b->err, JPGPU_ERR_UNSUPPORTED, "image %u: resample tables of the batch exceed 2^32 words", i);
     }
     for (uint32_t i = 0; i < n; i++) {  // (the tables stand still now)
         ResampleJob &j = b->rs_jobs[i];
-        if (!resample_plan(j, b->rs_tab.data())) return set_err(b->err, JPGPU_ERR_INTERNAL, "image %u: no resample plan", i);
-        b->rs_max_bands = std::max(b->rs_max_bands, j.bands);
+        if (b->placed) {
+            if (!placed_plan(j, b->rs_places[i], b->rs_tab.data())) return set_err(b->err, JPGPU_ERR_INTERNAL, "image %u: no resample plan", i);
+            b->rs_max_bands = std::max(b->rs_max_bands, b->rs_places[i].bands);
+        } else {
+            if (!resample_plan(j, b->rs_tab.data())) return set_err(b->err, JPGPU_ERR_INTERNAL, "image %u: no resample plan", i);
+            b->rs_max_bands = std::max(b->rs_max_bands, j.bands);
+        }
         b->rs_lds_bytes = std::max(b->rs_lds_bytes, j.lds_bytes);
     }
     B_HIP(batch_wait_enqueued(b));  // (a decode still queued reads the tables)
@@ -74,11 +107,24 @@ static int batch_upload_qt(jpgpu_batch *b) {
 // pinned mirror (fresh flips come with every call of a loader: a blocking copy per sub-batch would hold the uploader thread up).
 static int batch_upload_tensor_jobs(jpgpu_batch *b, hipStream_t stream) {
     const uint32_t n = (uint32_t)b->descs.size();
-    if (!b->h_tn_jobs) {
-        B_HIP(hipHostMalloc((void **)&b->h_tn_jobs, (size_t)n * sizeof(TensorJob), hipHostMallocDefault));
+    if (!b->h_tn_jobs && !b->h_ptn_jobs) {
+        if (b->placed) B_HIP(hipHostMalloc((void **)&b->h_ptn_jobs, (size_t)n * sizeof(PlacedTensorJob), hipHostMallocDefault));
+        else B_HIP(hipHostMalloc((void **)&b->h_tn_jobs, (size_t)n * sizeof(TensorJob), hipHostMallocDefault));
         B_HIP(hipEventCreateWithFlags(&b->tn_sent, hipEventDisableTiming));
     } else {
         B_HIP(hipEventSynchronize(b->tn_sent));  // (the copy before this one has read the mirror)
+    }
+    if (b->placed) {  // (the same records with every image's placement behind them)
+        for (uint32_t i = 0; i < n; i++) {
+            b->h_ptn_jobs[i].t.r = b->rs_jobs[i];
+            b->h_ptn_jobs[i].t.plane = b->rs_w * b->rs_h;
+            b->h_ptn_jobs[i].t.flip = b->tn_flips[i] ? 1u : 0u;
+            b->h_ptn_jobs[i].p = b->rs_places[i];
+        }
+        B_HIP(hipMemcpyAsync(b->d_ptn_jobs, b->h_ptn_jobs, (size_t)n * sizeof(PlacedTensorJob), hipMemcpyHostToDevice, stream));
+        B_HIP(hipEventRecord(b->tn_sent, stream));
+        b->tn_dirty = false;
+        return JPGPU_OK;
     }
     for (uint32_t i = 0; i < n; i++) {
         b->h_tn_jobs[i].r = b->rs_jobs[i];
@@ -159,6 +205,10 @@ static int batch_refresh_jobs(jpgpu_batch *b, hipStream_t stream = nullptr) {
         if (b->tn_es) {
             rc = batch_upload_tensor_jobs(b, stream);
             if (rc) return rc;
+        } else if (b->placed) {
+            std::vector<PlacedJob> pj(n);
+            for (uint32_t i = 0; i < n; i++) pj[i].r = b->rs_jobs[i], pj[i].p = b->rs_places[i];
+            B_HIP(hipMemcpy(b->d_pl_jobs, pj.data(), (size_t)n * sizeof(PlacedJob), hipMemcpyHostToDevice));
         } else {
             B_HIP(hipMemcpy(b->d_rs_jobs, b->rs_jobs.data(), (size_t)n * sizeof(ResampleJob), hipMemcpyHostToDevice));
         }
@@ -175,8 +225,10 @@ static int batch_refresh_jobs(jpgpu_batch *b, hipStream_t stream = nullptr) {
 extern "C" {
 
 // rs_w, rs_h: the output size of jpgpu_batch_create_resized (0, 0: none); tensor: the format of jpgpu_batch_create_tensor (NULL: none)
+// placements, fill: those of jpgpu_batch_create_placed (NULL: none)
 static int batch_create(int device, const jpgpu_image_desc *descs, const jpgpu_window *windows, uint32_t rs_w, uint32_t rs_h,
-                        const jpgpu_tensor_format *tensor, uint32_t n_images, uint32_t flags, jpgpu_batch **out) {
+                        const jpgpu_tensor_format *tensor, uint32_t n_images, uint32_t flags, jpgpu_batch **out,
+                        const jpgpu_placement *placements = nullptr, const uint8_t *fill = nullptr) {
     if (!out) return JPGPU_ERR_FORMAT;
     *out = nullptr;
     if (!descs || n_images == 0 || n_images > 65535) return JPGPU_ERR_FORMAT;
@@ -196,6 +248,19 @@ static int batch_create(int device, const jpgpu_image_desc *descs, const jpgpu_w
         for (uint32_t i = 0; i < n_images && !rgb; i++) nc_max = std::max(nc_max, std::min<uint32_t>(descs[i].ncomp, 4u));
         const char *why = nullptr;
         if (!tensor_format_ok(tensor->dtype, tensor->reserved, tensor->mean, tensor->std, nc_max, why)) return set_err(b->err, JPGPU_ERR_FORMAT, "tensor format: %s", why);
+    }
+    if (placements && resized) {  // (every placement shows a pixel; one that differs from the whole output makes the batch a placed one)
+        b->pl.assign(placements, placements + n_images);
+        for (uint32_t i = 0; i < n_images; i++) {
+            jpgpu_placement &pl = b->pl[i];
+            if (pl.rw == 0 || pl.rh == 0) pl = jpgpu_placement{(uint16_t)rs_w, (uint16_t)rs_h, 0, 0};
+            uint32_t first, count, v0;
+            if (!placed_axis(pl.rw, pl.x, rs_w, first, count, v0) || !placed_axis(pl.rh, pl.y, rs_h, first, count, v0))
+                return set_err(b->err, JPGPU_ERR_FORMAT, "image %u: the placement %ux%u at (%d, %d) shows no pixel of the %ux%u output", i, pl.rw, pl.rh, pl.x, pl.y,
+                               rs_w, rs_h);
+            if (pl.rw != rs_w || pl.rh != rs_h || pl.x != 0 || pl.y != 0) b->placed = true;
+        }
+        if (fill) b->pl_fill = (uint32_t)fill[0] | ((uint32_t)fill[1] << 8) | ((uint32_t)fill[2] << 16) | ((uint32_t)fill[3] << 24);
     }
     int rc = use_device(device, b->err);
     if (rc) return rc;
@@ -307,6 +372,7 @@ static int batch_create(int device, const jpgpu_image_desc *descs, const jpgpu_w
     if (!b->win.empty()) b->path = b->path.empty() ? "window" : "mixed";
     if (b->path.empty()) b->path = "generic";
     if (rgb) b->path += "+rgb";
+    if (b->placed) b->path += "+place";
     if (resized) b->path += "+resize";
     if (tensor) b->path += "+tensor";
     const size_t full = arena_layout(b->out_full_len);  // (what the whole images take)
@@ -322,13 +388,16 @@ static int batch_create(int device, const jpgpu_image_desc *descs, const jpgpu_w
         b->pix_cap = b->win.empty() ? b->pix_bytes : arena_headroom(b->pix_bytes, full);
         B_HIP(hipMalloc((void **)&b->d_pix, b->pix_cap));
         if (tensor) {  // (the table of four channels: every image looks up its own first ncomp rows)
-            B_HIP(hipMalloc((void **)&b->d_tn_jobs, (size_t)n_images * sizeof(TensorJob)));
+            if (b->placed) B_HIP(hipMalloc((void **)&b->d_ptn_jobs, (size_t)n_images * sizeof(PlacedTensorJob)));
+            else B_HIP(hipMalloc((void **)&b->d_tn_jobs, (size_t)n_images * sizeof(TensorJob)));
             B_HIP(hipMalloc(&b->d_tn_table, TN_TABLE_MAX));
             std::vector<uint32_t> table(TN_TABLE_MAX / 4u, 0u);
             uint32_t nc_max = rgb ? 3u : 1u;
             for (uint32_t i = 0; i < n_images && !rgb; i++) nc_max = std::max<uint32_t>(nc_max, b->descs[i].ncomp);
             tensor_table(tensor->dtype, tensor->mean, tensor->std, nc_max, table.data());
             B_HIP(hipMemcpy(b->d_tn_table, table.data(), TN_TABLE_MAX, hipMemcpyHostToDevice));
+        } else if (b->placed) {
+            B_HIP(hipMalloc((void **)&b->d_pl_jobs, (size_t)n_images * sizeof(PlacedJob)));
         } else {
             B_HIP(hipMalloc((void **)&b->d_rs_jobs, (size_t)n_images * sizeof(ResampleJob)));
         }
@@ -384,6 +453,17 @@ int jpgpu_batch_create_tensor(int device, const jpgpu_image_desc *descs, const j
     }
     return batch_create(device, descs, windows, out_w, out_h, format, n_images, flags, out);
 }
+int jpgpu_batch_create_placed(int device, const jpgpu_image_desc *descs, const jpgpu_window *windows, const jpgpu_placement *placements,
+                              const uint8_t *fill, uint16_t out_w, uint16_t out_h, const jpgpu_tensor_format *format, uint32_t n_images,
+                              uint32_t flags, jpgpu_batch **out) {
+    if (out_w == 0 || out_h == 0) {  // (0, 0 would mean "none" below: refuse it here)
+        if (!out) return JPGPU_ERR_FORMAT;
+        jpgpu_batch *b = new jpgpu_batch();
+        *out = b;
+        return set_err(b->err, JPGPU_ERR_FORMAT, "output size %ux%u: width and height must be 1..%u", out_w, out_h, RS_MAX_OUT);
+    }
+    return batch_create(device, descs, windows, out_w, out_h, format, n_images, flags, out, placements, fill);
+}
 int jpgpu_batch_set_flips(jpgpu_batch *b, const uint8_t *flips) {
     if (!b) return JPGPU_ERR_FORMAT;
     if (!b->tn_es) return set_err(b->err, JPGPU_ERR_UNSUPPORTED, "jpgpu_batch_set_flips: the batch has no tensor format");
@@ -403,6 +483,9 @@ void jpgpu_batch_destroy(jpgpu_batch *b) {
         if (b->d_pix) hipFree(b->d_pix);
         if (b->d_rs_jobs) hipFree(b->d_rs_jobs);
         if (b->d_tn_jobs) hipFree(b->d_tn_jobs);
+        if (b->d_pl_jobs) hipFree(b->d_pl_jobs);
+        if (b->d_ptn_jobs) hipFree(b->d_ptn_jobs);
+        if (b->h_ptn_jobs) hipHostFree(b->h_ptn_jobs);
         if (b->d_tn_table) hipFree(b->d_tn_table);
         if (b->h_tn_jobs) hipHostFree(b->h_tn_jobs);
         if (b->tn_sent) hipEventDestroy(b->tn_sent);
@@ -733,9 +816,24 @@ int jpgpu::batch_check_window(const jpgpu_image_desc &d, const jpgpu_window &wn,
 // output offsets / sizes and the job tables depend on the windows — the coefficient arena, the fused plans' membership and every
 // staging block stay.  JPGPU_ERR_UNSUPPORTED, with nothing changed, when another set of images would be windowed (or the buffers
 // are the caller's): the caller creates a new batch then.  The output arena grows when the new windows need more than it holds.
-int jpgpu::batch_rewindow(jpgpu_batch *b, const jpgpu_window *windows) {
+// `placements` (a placed batch; NULL: those it has): set with the windows.  A batch is placed or not for its lifetime — other device
+// job records, another launch — so placements for a batch without any, or none that differs from the whole output for a placed
+// one, are JPGPU_ERR_UNSUPPORTED too; one that shows no pixel is JPGPU_ERR_FORMAT.  Nothing is changed then.
+int jpgpu::batch_rewindow(jpgpu_batch *b, const jpgpu_window *windows, const jpgpu_placement *placements) {
     if (!b || !windows) return JPGPU_ERR_FORMAT;
     if ((!b->own_out && !b->rs_w) || b->win.empty()) return JPGPU_ERR_UNSUPPORTED;  // (with an output size the windows' bytes are the batch's own)
+    std::vector<jpgpu_placement> pls;
+    if (placements) {
+        bool any = false;
+        pls.assign(placements, placements + b->descs.size());
+        for (jpgpu_placement &pl : pls) {
+            if (pl.rw == 0 || pl.rh == 0) pl = jpgpu_placement{(uint16_t)b->rs_w, (uint16_t)b->rs_h, 0, 0};
+            uint32_t first, count, v0;
+            if (!placed_axis(pl.rw, pl.x, b->rs_w, first, count, v0) || !placed_axis(pl.rh, pl.y, b->rs_h, first, count, v0)) return JPGPU_ERR_FORMAT;
+            any = any || pl.rw != b->rs_w || pl.rh != b->rs_h || pl.x != 0 || pl.y != 0;
+        }
+        if (any != b->placed) return JPGPU_ERR_UNSUPPORTED;
+    }
     std::vector<WindowGeom> geoms;
     std::vector<size_t> lens;
     int rc = window_rule_rewindow(b->descs, b->win.ids, b->out_full_len, windows, geoms, lens);
@@ -753,6 +851,7 @@ int jpgpu::batch_rewindow(jpgpu_batch *b, const jpgpu_window *windows) {
         B_HIP(grow_device(w_arena, w_cap, w_bytes, arena_headroom(w_bytes, arena_layout(b->out_full_len))));
     }
     B_HIP(b->win.set_geoms(geoms, b->descs));
+    if (b->placed && placements) b->pl = pls;
     if (b->rs_w) return batch_resample_tables(b);
     return JPGPU_OK;
 }
@@ -864,7 +963,12 @@ int jpgpu_batch_decode(jpgpu_batch *b, void *hip_stream) {
         B_HIP(launch_window_band(b->win.d_geoms, b->win.d_image_jobs, b->win.d_plane_jobs, (uint32_t)b->win.ids.size(), b->win.max_tiles_x, b->win.max_bands,
                                  b->win.lds_bytes, b->win.scales, s));
     if (b->tn_es && b->tn_sent) B_HIP(hipStreamWaitEvent(s, b->tn_sent, 0));  // (the jobs may have gone up on another stream than this one)
-    if (b->tn_es)  // (a tensor output: the same resample, its vertical pass writes every image's tensor)
+    const bool rgb_out = (b->flags & JPGPU_BATCH_RGB_OUTPUT) != 0;
+    if (b->placed && b->tn_es)  // (placements: the kernels of placed.hip, for this batch only)
+        B_HIP(launch_resample_placed_tensor(b->d_ptn_jobs, b->d_rs_tab, b->d_tn_table, b->tn_es, (uint32_t)b->descs.size(), b->rs_max_bands, b->rs_lds_bytes, s, rgb_out));
+    else if (b->placed)
+        B_HIP(launch_resample_placed(b->d_pl_jobs, b->d_rs_tab, (uint32_t)b->descs.size(), b->rs_max_bands, b->rs_lds_bytes, s, rgb_out));
+    else if (b->tn_es)  // (a tensor output: the same resample, its vertical pass writes every image's tensor)
         B_HIP(launch_resample_tensor(b->d_tn_jobs, b->d_rs_tab, b->d_tn_table, b->tn_es, (uint32_t)b->descs.size(), b->rs_max_bands, b->rs_lds_bytes, s,
                                       (b->flags & JPGPU_BATCH_RGB_OUTPUT) != 0));
     else if (b->rs_w)  // (an output size: every image's pixels, wherever the launches above left them in the intermediate arena)

@@ -21,6 +21,7 @@
 #include "range_stats.hpp"
 #include "resample_band.hpp"
 #include "tensor_band.hpp"
+#include "placed_band.hpp"
 #include "window_band.hpp"
 
 using namespace jpgpu;
@@ -141,6 +142,16 @@ struct jpgpu_batch {
     TensorJob *h_tn_jobs = nullptr;    // pinned mirror the jobs travel from, on the decode's stream
     hipEvent_t tn_sent = nullptr;      // behind the last copy out of the mirror
     void *d_tn_table = nullptr;        // 4 x 256 elements
+    // Placements (jpgpu_batch_create_placed, placed_band.hpp; placed == false: none): some image of a batch with an output size is resampled
+    // to a size of its own and laid into the output with cropping / fill.  rs_jobs[i] is then the job of image i's visible rectangle (tables
+    // of the visible range), rs_places[i] where it lies; the device jobs are PlacedJobs / PlacedTensorJobs and the launch is placed.hip's.
+    bool placed = false;
+    std::vector<jpgpu_placement> pl;   // per image, "none" written out as (rs_w, rs_h, 0, 0)
+    uint32_t pl_fill = 0;              // fill[c] in byte c
+    std::vector<Place> rs_places;      // per image
+    PlacedJob *d_pl_jobs = nullptr;
+    PlacedTensorJob *d_ptn_jobs = nullptr;
+    PlacedTensorJob *h_ptn_jobs = nullptr;  // pinned mirror, as h_tn_jobs
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
     // Behind the last work enqueued on a caller's stream that reads the batch's tables or its coefficient arena (every decode,
     // jpgpu_batch_classify_on_device).  That stream may be a non-blocking one, which a blocking copy on the null stream does not order

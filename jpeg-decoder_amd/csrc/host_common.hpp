@@ -55,7 +55,7 @@ int batch_check_window(const jpgpu_image_desc &d, const jpgpu_window &wn, bool &
 uint32_t batch_windowed_images(const jpgpu_batch *b);  // images of the batch in the window group
 bool batch_image_windowed(const jpgpu_batch *b, uint32_t image);  // ... is this one of them (its pixels come from the window kernel)
 // other windows for the same window group of an idle batch, in place (batch.cpp); JPGPU_ERR_UNSUPPORTED: create a new batch instead
-int batch_rewindow(jpgpu_batch *b, const jpgpu_window *windows);
+int batch_rewindow(jpgpu_batch *b, const jpgpu_window *windows, const jpgpu_placement *placements = nullptr);
 size_t batch_out_arena_bound(const jpgpu_batch *b);  // jpgpu_batch_out_arena_bytes of the same images without windows
 
 // before a worker goes back to the decoder API's pool of idle workers

@@ -12,6 +12,7 @@
 #include "compact.hpp"
 #include "resample_band.hpp"
 #include "tensor_band.hpp"
+#include "placed_band.hpp"
 
 namespace jpgpu {
 
@@ -192,6 +193,25 @@ int jpgpu_resample_coefficients(uint32_t in_size, uint32_t out_size, int32_t *bo
     if (in_size == 0 || out_size == 0 || in_size > 65535u || out_size > 65535u || !ksize || (!bounds) != (!coefs)) return JPGPU_ERR_FORMAT;
     *ksize = jpgpu::resample_ksize(in_size, out_size);
     if (bounds) jpgpu::resample_coefficients(in_size, out_size, bounds, coefs, *ksize);
+    return JPGPU_OK;
+}
+
+// entries [first, first + count) of the same tables (placed_band.hpp; the batch fills a placed image's with the same function)
+int jpgpu_resample_coefficients_range(uint32_t in_size, uint32_t out_size, uint32_t first, uint32_t count, int32_t *bounds, int32_t *coefs, uint32_t *ksize) {
+    if (in_size == 0 || out_size == 0 || in_size > 65535u || out_size > 65535u || !ksize || (!bounds) != (!coefs)) return JPGPU_ERR_FORMAT;
+    if (first > out_size || count > out_size - first) return JPGPU_ERR_FORMAT;
+    *ksize = jpgpu::resample_ksize(in_size, out_size);
+    if (bounds) jpgpu::resample_coefficients_range(in_size, out_size, first, count, bounds, coefs, *ksize);
+    return JPGPU_OK;
+}
+
+// the placement rules (placed_band.hpp; the pipeline places every image with the same function)
+int jpgpu_fit_placement(const jpgpu_fit *fit, uint32_t src_w, uint32_t src_h, uint32_t out_w, uint32_t out_h, jpgpu_placement *out) {
+    if (!fit || !out || fit->reserved != 0) return JPGPU_ERR_FORMAT;
+    uint32_t rw = 0, rh = 0;
+    int32_t x = 0, y = 0;
+    if (!jpgpu::fit_placement(fit->mode, fit->size, src_w, src_h, out_w, out_h, rw, rh, x, y)) return JPGPU_ERR_FORMAT;
+    out->rw = (uint16_t)rw, out->rh = (uint16_t)rh, out->x = x, out->y = y;
     return JPGPU_OK;
 }
 

@@ -262,6 +262,9 @@ struct SubBatch {
     jpgpu_tensor_format tn{};
     bool rgb = false;                 // created with JPGPU_BATCH_RGB_OUTPUT (jpgpu_pipeline_set_rgb_output)
     std::vector<uint8_t> flips;       // a tensor batch: the flip of every image as the batch holds it (jpgpu_batch_set_flips)
+    bool fit_on = false;              // created with placements under this rule (jpgpu_pipeline_set_fit)
+    jpgpu_fit fit{};
+    std::vector<jpgpu_placement> pls; // ... the placement of every image as the batch holds it
     uint32_t remaining = 0;  // images not yet uploaded / failed (uploader thread only)
     hipEvent_t ready[kCopyStreams] = {nullptr, nullptr, nullptr, nullptr};
     hipEvent_t decoded = nullptr;  // recorded on the compute stream behind the sub-batch's pixel kernels: downloads and the gather wait for it
@@ -279,6 +282,9 @@ struct SubBatch {
         tensor = false;
         rgb = false;
         flips.clear();
+        fit_on = false;
+        fit = jpgpu_fit{};
+        pls.clear();
     }
 };
 
@@ -305,6 +311,7 @@ struct jpgpu_pipeline {
     std::vector<std::string> errors;
     std::vector<jpgpu_image_info> infos;
     std::vector<jpgpu_window> wins;  // per image: the window decoded (jpgpu_pipeline_image_window; the whole output grid when there was none)
+    std::vector<jpgpu_placement> places;  // per image: its placement in the output size (jpgpu_pipeline_image_placement; rw == 0: none)
     std::vector<int32_t> sub_of, slot;  // image -> sub-batch / index in it, -1 if it never got there
     std::vector<std::vector<jpgpu::host::PlannedScan>> plans;  // per image: scans for the device entropy decoder (empty: host)
     std::vector<jpgpu::host::ProgPlan> prog_plans;             // per image: the scans of a PROGRESSIVE frame for the device (no scans: host)
@@ -321,6 +328,8 @@ struct jpgpu_pipeline {
     uint16_t rs_w = 0, rs_h = 0;    // jpgpu_pipeline_set_output_size (0 x 0: none)
     bool tensor = false;            // jpgpu_pipeline_set_tensor_output
     bool rgb = false;               // jpgpu_pipeline_set_rgb_output
+    bool fit_on = false;            // jpgpu_pipeline_set_fit (a rule other than stretch)
+    jpgpu_fit fit{};
     jpgpu_tensor_format tn{};
     int color_transform = -1;       // jpgpu_pipeline_set_color_transform (< 0: what every image says itself)
     size_t max_bytes = SIZE_MAX;    // jpgpu_pipeline_set_max_decoding_buffer_size
@@ -642,6 +651,7 @@ int jpgpu_pipeline_decode_augmented(jpgpu_pipeline *p, const uint8_t *const *dat
     // (a tensor output needs an output size, flips a tensor output: refused before anything is decoded)
     if (p && p->tensor && !p->rs_w) return jpgpu::set_err(p->err, JPGPU_ERR_FORMAT, "jpgpu_pipeline_decode: a tensor output needs an output size (jpgpu_pipeline_set_output_size)");
     if (p && p->rgb && !p->rs_w) return jpgpu::set_err(p->err, JPGPU_ERR_FORMAT, "jpgpu_pipeline_decode: RGB output needs an output size (jpgpu_pipeline_set_output_size)");
+    if (p && p->fit_on && !p->rs_w) return jpgpu::set_err(p->err, JPGPU_ERR_FORMAT, "jpgpu_pipeline_decode: a fit needs an output size (jpgpu_pipeline_set_output_size)");
     if (p && flips && !p->tensor) return jpgpu::set_err(p->err, JPGPU_ERR_FORMAT, "jpgpu_pipeline_decode_augmented: flips need a tensor output (jpgpu_pipeline_set_tensor_output)");
     if (p && !p->children.empty()) return (n && (!data || !len)) ? JPGPU_ERR_FORMAT : multi_decode(p, data, len, windows, flips, n, flags);
     if (!p || !p->pool || (n && (!data || !len))) return JPGPU_ERR_FORMAT;
@@ -660,6 +670,7 @@ int jpgpu_pipeline_decode_augmented(jpgpu_pipeline *p, const uint8_t *const *dat
     p->errors.assign(n, std::string());
     p->infos.assign(n, jpgpu_image_info{});
     p->wins.assign(n, jpgpu_window{0, 0, 0, 0});
+    p->places.assign(n, jpgpu_placement{0, 0, 0, 0});
     p->sub_of.assign(n, -1);
     p->plans.clear();
     p->plans.resize(n);
@@ -748,6 +759,14 @@ int jpgpu_pipeline_decode_augmented(jpgpu_pipeline *p, const uint8_t *const *dat
                 // (an output size: planar output has no resample — the image fails alone, like a refused window)
                 if (p->rs_w && planar)
                     throw DecodeError{JPGPU_ERR_UNSUPPORTED, "no output size for planar output (ColorTransform None with more than one component)"};
+                if (p->rs_w) p->places[i] = jpgpu_placement{p->rs_w, p->rs_h, 0, 0};
+                // (a fit: the placement of THIS image's source — its window, else its output grid; a refused rule fails the image alone)
+                if (p->fit_on && jpgpu_fit_placement(&p->fit, p->wins[i].w, p->wins[i].h, p->rs_w, p->rs_h, &p->places[i]) != JPGPU_OK) {
+                    char msg[160];
+                    snprintf(msg, sizeof msg, "fit: no placement of a %ux%u source in %ux%u (a resampled side above 65535)", p->wins[i].w, p->wins[i].h, p->rs_w, p->rs_h);
+                    p->places[i] = jpgpu_placement{0, 0, 0, 0};
+                    throw DecodeError{JPGPU_ERR_FORMAT, msg};
+                }
                 const char *bad = nullptr;  // (the format's means and stds against THIS image's channels)
                 if (p->tensor && !jpgpu::tensor_format_ok(p->tn.dtype, p->tn.reserved, p->tn.mean, p->tn.std, p->rgb ? 3u : d.ncomp, bad))
                     throw DecodeError{JPGPU_ERR_FORMAT, std::string("tensor format: ") + bad};
@@ -852,6 +871,7 @@ int jpgpu_pipeline_decode_augmented(jpgpu_pipeline *p, const uint8_t *const *dat
         std::vector<jpgpu_image_desc> descs;
         std::vector<jpgpu_window> wins;  // (stays empty when no image of the sub-batch has a window: jpgpu_batch_create's own path)
         std::vector<uint8_t> fl;         // a tensor output: every image's flip
+        std::vector<jpgpu_placement> pls;  // a fit: every image's placement
         bool sub_windowed = false;
         for (uint32_t k = first; any_window && k < last; k++) sub_windowed = sub_windowed || win[ok[k]].w != 0;
         for (uint32_t k = first; k < last; k++) {
@@ -860,6 +880,7 @@ int jpgpu_pipeline_decode_augmented(jpgpu_pipeline *p, const uint8_t *const *dat
             descs.push_back(cand[ok[k]]);
             if (sub_windowed) wins.push_back(win[ok[k]]);
             if (p->tensor) fl.push_back(flips && flips[ok[k]] ? 1 : 0);
+            if (p->fit_on) pls.push_back(p->places[ok[k]]);
         }
         sb.remaining = last - first;
         // Sub-batches of device-entropy images need no pinned staging for coefficients (their entropy-coded bytes are staged by
@@ -869,6 +890,9 @@ int jpgpu_pipeline_decode_augmented(jpgpu_pipeline *p, const uint8_t *const *dat
         // (another output size: other tables, another output arena — the sub-batch is created anew)
         bool reuse = sb.batch && descs.size() == sb.descs.size() && sb.compact == compact && (sb.h_coef != nullptr) == staged && sb.rs_w == p->rs_w && sb.rs_h == p->rs_h &&
                      sb.rgb == p->rgb && sb.tensor == p->tensor && (!p->tensor || memcmp(&sb.tn, &p->tn, sizeof(jpgpu_tensor_format)) == 0);  // (... or another tensor format)
+        // (... or another fit: the batch is placed or not, and holds the fill, for its lifetime)
+        reuse = reuse && sb.fit_on == p->fit_on && (!p->fit_on || memcmp(&sb.fit, &p->fit, sizeof(jpgpu_fit)) == 0);
+        const bool same_pls = pls.size() == sb.pls.size() && (pls.empty() || memcmp(pls.data(), sb.pls.data(), pls.size() * sizeof(jpgpu_placement)) == 0);
         for (size_t k = 0; reuse && k < descs.size(); k++) reuse = same_geometry(descs[k], sb.descs[k]);
         // ... and the same windows: the window group's geometry and the output offsets are made from them (a kept batch with other
         // windows would return the pixels of the old ones).  Other windows for the SAME set of windowed images — a loader's fresh
@@ -879,14 +903,18 @@ int jpgpu_pipeline_decode_augmented(jpgpu_pipeline *p, const uint8_t *const *dat
         if (reuse && !(wins.size() == sb.wins.size() && (wins.empty() || memcmp(wins.data(), sb.wins.data(), wins.size() * sizeof(jpgpu_window)) == 0))) {
             const char *rw = getenv("JPGPU_PIPE_REWINDOW");
             int rrc = JPGPU_ERR_UNSUPPORTED;
-            if (!wins.empty() && !sb.wins.empty() && !(rw && atoi(rw) == 0)) rrc = jpgpu::batch_rewindow(sb.batch, wins.data());
-            if (rrc == JPGPU_OK) sb.wins = wins, how = "re-windowed in place";
+            if (!wins.empty() && !sb.wins.empty() && !(rw && atoi(rw) == 0)) rrc = jpgpu::batch_rewindow(sb.batch, wins.data(), pls.empty() ? nullptr : pls.data());
+            if (rrc == JPGPU_OK) sb.wins = wins, sb.pls = pls, how = "re-windowed in place";  // (fresh windows at the same fit: re-placed with them)
             else reuse = false, how = "created (other windows)";
+        } else if (reuse && !same_pls) {
+            reuse = false, how = "created (other placements)";
         }
         if (!reuse) {
             sb.drop();
             const uint32_t bf = p->rgb ? JPGPU_BATCH_RGB_OUTPUT : JPGPU_BATCH_DEFAULT;  // (every image three channels: the batch's resample converts)
-            rc = p->tensor ? jpgpu_batch_create_tensor(p->device, descs.data(), wins.empty() ? nullptr : wins.data(), p->rs_w, p->rs_h, &p->tn, (uint32_t)descs.size(), bf, &sb.batch)
+            rc = p->fit_on ? jpgpu_batch_create_placed(p->device, descs.data(), wins.empty() ? nullptr : wins.data(), pls.data(), p->fit.fill, p->rs_w, p->rs_h,
+                                                       p->tensor ? &p->tn : nullptr, (uint32_t)descs.size(), bf, &sb.batch)
+                 : p->tensor ? jpgpu_batch_create_tensor(p->device, descs.data(), wins.empty() ? nullptr : wins.data(), p->rs_w, p->rs_h, &p->tn, (uint32_t)descs.size(), bf, &sb.batch)
                  : p->rs_w ? jpgpu_batch_create_resized(p->device, descs.data(), wins.empty() ? nullptr : wins.data(), p->rs_w, p->rs_h, (uint32_t)descs.size(), bf, &sb.batch)
                          : jpgpu_batch_create_windowed(p->device, descs.data(), wins.empty() ? nullptr : wins.data(), (uint32_t)descs.size(), JPGPU_BATCH_DEFAULT, &sb.batch);
             if (rc) {
@@ -907,6 +935,7 @@ int jpgpu_pipeline_decode_augmented(jpgpu_pipeline *p, const uint8_t *const *dat
             sb.rs_w = p->rs_w, sb.rs_h = p->rs_h;
             sb.tensor = p->tensor, sb.tn = p->tn;
             sb.rgb = p->rgb;
+            sb.fit_on = p->fit_on, sb.fit = p->fit, sb.pls = pls;
             sb.flips.assign(descs.size(), 0);
             sb.compact = compact;
             sb.h_coef_bytes = jpgpu_batch_coef_arena_bytes(sb.batch);
@@ -1460,6 +1489,22 @@ int jpgpu_pipeline_set_tensor_output(jpgpu_pipeline *p, const jpgpu_tensor_forma
     for (jpgpu_pipeline *c : p->children) jpgpu_pipeline_set_tensor_output(c, format);
     p->tensor = format != nullptr;
     p->tn = format ? *format : jpgpu_tensor_format{};
+    return JPGPU_OK;
+}
+int jpgpu_pipeline_set_fit(jpgpu_pipeline *p, const jpgpu_fit *fit) {
+    if (!p) return JPGPU_ERR_FORMAT;
+    if (fit && (fit->mode > JPGPU_FIT_LETTERBOX || fit->reserved != 0 || (fit->mode == JPGPU_FIT_SHORTER_SIDE_CROP && fit->size == 0)))
+        return jpgpu::set_err(p->err, JPGPU_ERR_FORMAT, "fit: mode %u, size %u, reserved %u (mode must be 0..2, size non-zero for mode 1, reserved 0)", fit->mode, fit->size,
+                              fit->reserved);
+    for (jpgpu_pipeline *c : p->children) jpgpu_pipeline_set_fit(c, fit);
+    p->fit_on = fit != nullptr && fit->mode != JPGPU_FIT_STRETCH;  // (stretch: every placement is the whole output — no placement at all)
+    p->fit = p->fit_on ? *fit : jpgpu_fit{};
+    return JPGPU_OK;
+}
+int jpgpu_pipeline_image_placement(const jpgpu_pipeline *p, uint32_t i, jpgpu_placement *out) {
+    MULTI(p, i, jpgpu_pipeline_image_placement(c, ci, out), JPGPU_ERR_FORMAT)
+    if (!p || i >= p->n || !out || i >= p->places.size() || p->places[i].rw == 0 || p->places[i].rh == 0) return JPGPU_ERR_FORMAT;
+    *out = p->places[i];
     return JPGPU_OK;
 }
 int jpgpu_pipeline_set_rgb_output(jpgpu_pipeline *p, int on) {

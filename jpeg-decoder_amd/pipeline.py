@@ -76,7 +76,7 @@ class Pipeline:
 
     def decode(self, streams, download=True, dense=False, device_entropy=True, scale=None, color_transform=None, max_decoding_buffer_size=None,
                gather=False, host_light=None, input_pinned=False, progressive_on_host=False, windows=None, output_size=None,
-               tensor=None, flips=None, rgb=False):
+               tensor=None, flips=None, rgb=False, fit=None):
         """-> list with, per stream, a numpy uint8 array of the decoded pixels (``Decoder.decode()``'s Vec<u8>) or the
         ``Error`` instance that stream produced.  download=False leaves the pixels in HBM (see ``device_pointer``); dense=True sends all
         64 coefficients of every block over PCIe instead of the compact form (same pixels, A/B switch); device_entropy=True
@@ -107,7 +107,12 @@ class Pipeline:
         decoded).  Fresh windows and flips for the same files keep the pipeline's sub-batches.
         rgb: True (jpgpu_pipeline_set_rgb_output, set on every call; needs output_size, else FormatError and nothing is decoded): every
         stream gives three channels — gray replicated, CMYK / YCCK converted as Pillow's ``convert("RGB")`` does, before the resample
-         — so arrays are (h * w * 3,) uint8 or (3, h, w); ``info(i)`` keeps the file's own components."""
+         — so arrays are (h * w * 3,) uint8 or (3, h, w); ``info(i)`` keeps the file's own components.
+        fit: None or a ``Fit`` (jpgpu_pipeline_set_fit, set on every call; needs output_size, else FormatError and nothing is decoded):
+        every stream's source — its window, else its output after `scale` — is resampled to a size of its own and laid into the output
+        size, cropped and filled: ``Fit("shorter_side_crop", size=256)`` with output_size=(224, 224) is the evaluation
+        transform ``Resize(256)`` + ``CenterCrop(224)``, ``Fit("letterbox", fill=(114, 114, 114))`` the aspect-preserving fit with constant
+        padding.  ``placement(i)`` gives the stream's (rw, rh, x, y); a stream whose rule is refused (a side above 65535) fails alone."""
         if isinstance(streams, PinnedFiles):
             bufs = None
             n = len(streams)
@@ -130,6 +135,9 @@ class Pipeline:
         st = L.jpgpu_pipeline_set_tensor_output(self._h, None if fmt is None else C.byref(fmt))
         check(st, L.jpgpu_pipeline_last_error(self._h) if st else b"")
         check(L.jpgpu_pipeline_set_rgb_output(self._h, 1 if rgb else 0), b"set_rgb_output")
+        fit_s = None if fit is None else fit.struct()
+        st = L.jpgpu_pipeline_set_fit(self._h, None if fit_s is None else C.byref(fit_s))
+        check(st, L.jpgpu_pipeline_last_error(self._h) if st else b"")
         if bufs is None:
             ptrs = (C.c_void_p * max(n, 1))(*[streams.base + o for o in streams.offsets])
             lens = (C.c_size_t * max(n, 1))(*streams.lengths)
@@ -174,6 +182,14 @@ class Pipeline:
         if N.lib().jpgpu_pipeline_image_info(self._h, image, C.byref(i)):
             return None
         return ImageInfo(i.width, i.height, PIXEL_FORMATS[i.pixel_format], CODING_PROCESSES[i.coding_process])
+
+    def placement(self, image):
+        """jpgpu_pipeline_image_placement: (rw, rh, x, y) the image of the last call was placed with in the output size — (w, h, 0, 0)
+        without a fit; None for an image without one (no output size, no frame, a refused window or rule)."""
+        pl = N.Placement()
+        if N.lib().jpgpu_pipeline_image_placement(self._h, image, C.byref(pl)):
+            return None
+        return pl.rw, pl.rh, pl.x, pl.y
 
     def window(self, image):
         """jpgpu_pipeline_image_window: (x, y, w, h) the image of the last call was decoded with — (0, 0, W, H) of its output grid
