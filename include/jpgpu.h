@@ -142,6 +142,7 @@ enum {
     JPGPU_BATCH_FORCE_GENERIC = 2,    /* never take the fused fast paths (two-kernel path)  */
     JPGPU_BATCH_ASSUME_HOSTILE = 4,   /* skip the range scan: always use the exact 32-bit path */
     JPGPU_BATCH_RGB_OUTPUT = 8,       /* with an output size: every image gives three channels (see below) */
+    /* bits 8..11: the resample filter of a batch with an output size, JPGPU_BATCH_FILTER(JPGPU_FILTER_*) (see "Resample filters") */
 };
 
 int jpgpu_batch_create(int device, const jpgpu_image_desc *descs, uint32_t n_images,
@@ -190,6 +191,35 @@ int jpgpu_batch_create_resized(int device, const jpgpu_image_desc *descs, const 
  * (xmin, n), `coefs` out_size x ksize int32 weights, zero beyond n; *ksize the row length.  With `bounds` and `coefs` NULL only
  * *ksize is set (to size the buffers).  in_size and out_size are 1..65535; anything else is JPGPU_ERR_FORMAT. */
 int jpgpu_resample_coefficients(uint32_t in_size, uint32_t out_size, int32_t *bounds, int32_t *coefs, uint32_t *ksize);
+/* ---- Resample filters: Pillow's BOX, BILINEAR, HAMMING, BICUBIC and LANCZOS ---------------------------------------------------------
+ * JPGPU_BATCH_FILTER(f) in the `flags` of jpgpu_batch_create_resized / _create_tensor / _create_placed picks the filter of every
+ * resample of the batch (every image, both axes; a placed image's resample to rw x rh).  0 = JPGPU_FILTER_BILINEAR, so flags without
+ * the bits give what they always gave — tables, kernels, bytes and jpgpu_batch_path.  With another filter the result is Pillow's
+ * Image.resize(size, F) on the cropped image: rules 1-6 above with three changes.
+ *   1'. support = S_F * fs with S_F = 1 (BILINEAR), 0.5 (BOX), 1 (HAMMING), 2 (BICUBIC), 3 (LANCZOS); ksize = ceil(support) * 2 + 1; xmin,
+ *       xmax, n and ss as in rules 1-2 with this support.
+ *   3'. w[x] = f((x + xmin - center + 0.5) * ss) on the SIGNED argument, in IEEE double, one operation per statement (no FMA), sin and
+ *       cos the C library's:
+ *         BOX       1 if -0.5 < x <= 0.5, else 0
+ *         BILINEAR  x = |x|;  x < 1 ? 1 - x : 0
+ *         HAMMING   x = |x|;  x == 0: 1;  x >= 1: 0;  x = x * pi;  sin(x) / x * (0.54f + 0.46f * cos(x)) — the two constants are FLOAT
+ *                   literals promoted to double
+ *         BICUBIC   a = -0.5;  x = |x|;  x < 1: ((a + 2) x - (a + 3)) x x + 1;  x < 2: (((x - 5) x + 8) x - 4) a;  else 0
+ *         LANCZOS   -3 <= x < 3: sinc(x) * sinc(x / 3), else 0;  sinc(0) = 1, sinc(x) = sin(x pi) / (x pi)
+ *   4'. v = w[x] / ww (w[x] itself where ww == 0);  k[x] = v < 0 ? (int)(-0.5 + v * 2^22) : (int)(0.5 + v * 2^22).  Weights can be
+ *       negative; both passes clamp to 0..255 as rule 5 states; 255 * sum |k[x]| + 2^21 stays below 2^31 (tests/test_filters.py sweeps it),
+ *       so partial sums are exact in 32 bits in any order.
+ * An axis whose size does not change yields k = {2^22} under every filter.  jpgpu_batch_path names a filter other than BILINEAR behind
+ * "+resize": "+resize:bicubic", "+resize:lanczos+tensor"; and "+roll" at its end where some image's resample runs in runs of bands (BICUBIC
+ * and LANCZOS plans whose row bands overlap by more than 1.3: workgroups that keep the shared source rows in LDS — same bytes).  Refusals: a filter other than 0 on jpgpu_batch_create / _create_windowed (no
+ * output size): JPGPU_ERR_UNSUPPORTED, as RGB output; an id above 4: JPGPU_ERR_FORMAT. */
+enum { JPGPU_FILTER_BILINEAR = 0, JPGPU_FILTER_BOX = 1, JPGPU_FILTER_HAMMING = 2, JPGPU_FILTER_BICUBIC = 3, JPGPU_FILTER_LANCZOS = 4 };
+#define JPGPU_BATCH_FILTER(f) (((uint32_t)(f) & 15u) << 8)
+/* jpgpu_resample_coefficients / jpgpu_resample_coefficients_range (below) under a filter; filter 0 gives exactly what they give.  An
+ * id above 4: JPGPU_ERR_FORMAT. */
+int jpgpu_resample_coefficients_filtered(uint32_t filter, uint32_t in_size, uint32_t out_size, int32_t *bounds, int32_t *coefs, uint32_t *ksize);
+int jpgpu_resample_coefficients_range_filtered(uint32_t filter, uint32_t in_size, uint32_t out_size, uint32_t first, uint32_t count, int32_t *bounds,
+                                               int32_t *coefs, uint32_t *ksize);
 /* ---- A tensor output: every image resampled, normalised and written channel-first, as the model reads it -----------------------
  * jpgpu_batch_create_resized with a tensor format.  The output of image i is ncomp x out_h x out_w elements of `dtype`, planar (CHW)
  * and packed:
@@ -252,7 +282,8 @@ int jpgpu_tensor_table(const jpgpu_tensor_format *format, uint32_t nc, void *tab
  *                  = fill[c]              otherwise
  *   - the source is the image's window, or its whole output, in the grid after the DCT scale — the source of the fixed output size,
  *     after the RGB conversion when JPGPU_BATCH_RGB_OUTPUT is set;
- *   - R follows rules 1-6 of jpgpu_batch_create_resized with out_size = rw / rh, the horizontal pass first;
+ *   - R follows rules 1-6 of jpgpu_batch_create_resized (under the batch's filter, JPGPU_BATCH_FILTER) with out_size = rw / rh, the
+ *     horizontal pass first;
  *   - `fill` is four bytes per batch in the output's channel order (NULL: zeros);
  *   - the Pillow equivalent is canvas = Image.new(mode, (out_w, out_h), fill); canvas.paste(src.resize((rw, rh), BILINEAR), (x, y));
  *   - with a tensor format the element is T[c][out(r, flip ? out_w - 1 - x : x, c)]: a filled element is T[c][fill[c]] — what Pad(fill)

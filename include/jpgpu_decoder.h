@@ -248,6 +248,13 @@ int jpgpu_pipeline_set_tensor_output(jpgpu_pipeline *p, const jpgpu_tensor_forma
  * hold / count the three-channel bytes; jpgpu_pipeline_image_info keeps reporting the file's own components and pixel format.
  * Switching it on or off between calls creates the kept sub-batches anew, as a changed output size does. */
 int jpgpu_pipeline_set_rgb_output(jpgpu_pipeline *p, int on);
+/* The resample filter for every image of the calls that follow (sticky, like the output size): one of JPGPU_FILTER_* (jpgpu.h); the
+ * sub-batches are created with JPGPU_BATCH_FILTER(filter).  JPGPU_FILTER_BILINEAR (0) is the default: the tables, kernels, bytes and path
+ * string of the output size alone.  Another filter needs an output size: with none in force the next decode fails as a whole with
+ * JPGPU_ERR_FORMAT before anything is decoded.  An id above 4: JPGPU_ERR_FORMAT, nothing changes.  A changed filter creates the kept
+ * sub-batches anew; fresh windows at the same filter are set in place (their tables are made with it).  Composes with the scale, the
+ * tensor format, flips, RGB output, a fit and windows. */
+int jpgpu_pipeline_set_filter(jpgpu_pipeline *p, uint32_t filter);
 /* A placement rule for every image of the calls that follow (sticky, like the output size): each image's source — its window's
  * size, else its output's, after jpgpu_pipeline_set_scale — is placed in the output size by jpgpu_fit_placement(fit, ...) of its own
  * size, and its sub-batch is created with jpgpu_batch_create_placed (jpgpu.h: resampled to a size of its own, cropped, filled with

@@ -31,6 +31,13 @@ OK, ERR_FORMAT, ERR_UNSUPPORTED, ERR_IO, ERR_INTERNAL, ERR_NO_DEVICE = range(6)
 MAX_COMPONENTS = 4
 
 BATCH_DEFAULT, BATCH_EXTERNAL_BUFFERS, BATCH_FORCE_GENERIC, BATCH_ASSUME_HOSTILE, BATCH_RGB_OUTPUT = 0, 1, 2, 4, 8
+FILTER_BILINEAR, FILTER_BOX, FILTER_HAMMING, FILTER_BICUBIC, FILTER_LANCZOS = range(5)
+FILTER_NAMES = ("bilinear", "box", "hamming", "bicubic", "lanczos")
+
+
+def BATCH_FILTER(f):
+    """JPGPU_BATCH_FILTER: the filter id in bits 8..11 of a batch's flags."""
+    return (int(f) & 15) << 8
 
 
 class Component(C.Structure):
@@ -154,6 +161,8 @@ _PROTOS = {
     "jpgpu_fit_placement": (C.c_int, [C.POINTER(FitStruct), C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(Placement)]),
     "jpgpu_batch_set_flips": (C.c_int, [C.c_void_p, C.c_void_p]),
     "jpgpu_tensor_table": (C.c_int, [C.POINTER(TensorFormatStruct), C.c_uint32, C.c_void_p]),
+    "jpgpu_resample_coefficients_filtered": (C.c_int, [C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.POINTER(C.c_uint32)]),
+    "jpgpu_resample_coefficients_range_filtered": (C.c_int, [C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.POINTER(C.c_uint32)]),
     "jpgpu_resample_coefficients": (C.c_int, [C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.POINTER(C.c_uint32)]),
     "jpgpu_batch_destroy": (None, [C.c_void_p]),
     "jpgpu_batch_last_error": (C.c_char_p, [C.c_void_p]),
@@ -225,6 +234,7 @@ _PROTOS = {
     "jpgpu_pipeline_set_output_size": (C.c_int, [C.c_void_p, C.c_uint16, C.c_uint16]),
     "jpgpu_pipeline_set_tensor_output": (C.c_int, [C.c_void_p, C.POINTER(TensorFormatStruct)]),
     "jpgpu_pipeline_set_rgb_output": (C.c_int, [C.c_void_p, C.c_int]),
+    "jpgpu_pipeline_set_filter": (C.c_int, [C.c_void_p, C.c_uint32]),
     "jpgpu_pipeline_set_fit": (C.c_int, [C.c_void_p, C.POINTER(FitStruct)]),
     "jpgpu_pipeline_image_placement": (C.c_int, [C.c_void_p, C.c_uint32, C.POINTER(Placement)]),
     "jpgpu_pipeline_set_color_transform": (C.c_int, [C.c_void_p, C.c_int]),

@@ -123,6 +123,35 @@ def fill_tuple(fill):
     return tuple(fill + [0] * (4 - len(fill)))
 
 
+def filter_id(filter):
+    """`filter`: None (bilinear), one of "bilinear", "box", "hamming", "bicubic", "lanczos" (any case), or a JPGPU_FILTER_* id (an id
+    the library does not know is refused there: FormatError) -> the id."""
+    if filter is None:
+        return N.FILTER_BILINEAR
+    if isinstance(filter, str):
+        name = filter.lower()
+        if name not in N.FILTER_NAMES:
+            raise ValueError(f"filter {filter!r}: one of {', '.join(N.FILTER_NAMES)}")
+        return N.FILTER_NAMES.index(name)
+    f = int(filter)
+    if not 0 <= f <= 15:
+        raise ValueError(f"filter id {f}: 0..15")
+    return f
+
+
+def resample_coefficients(in_size, out_size, filter=None):
+    """jpgpu_resample_coefficients_filtered: the tables of one axis as the batch computes them (pure host function) -> (bounds int32
+    (out_size, 2) of (xmin, n), coefs int32 (out_size, ksize), zero beyond n)."""
+    f = filter_id(filter)
+    ks = C.c_uint32(0)
+    check(N.lib().jpgpu_resample_coefficients_filtered(f, int(in_size), int(out_size), None, None, C.byref(ks)), b"jpgpu_resample_coefficients_filtered: refused")
+    bounds = np.zeros((int(out_size), 2), np.int32)
+    coefs = np.zeros((int(out_size), ks.value), np.int32)
+    check(N.lib().jpgpu_resample_coefficients_filtered(f, int(in_size), int(out_size), bounds.ctypes.data, coefs.ctypes.data, C.byref(ks)),
+          b"jpgpu_resample_coefficients_filtered: refused")
+    return bounds, coefs
+
+
 def fit_placement(fit, src_size, output_size):
     """jpgpu_fit_placement: the placement (rw, rh, x, y) of a source of ``src_size`` = (w, h) in ``output_size`` = (w, h) under ``fit``
     (a Fit, or a raw N.FitStruct).  A refused rule (a side above 65535, an unknown mode) raises FormatError."""
@@ -193,9 +222,14 @@ class Batch:
     is cropped, what it does not cover is ``fill`` (up to four bytes, the output's channel order).  Pillow's
     ``canvas = Image.new(mode, (w, h), fill); canvas.paste(src.resize((rw, rh), BILINEAR), (x, y))``; with a tensor a filled element is
     ``T[c][fill[c]]`` and a flip mirrors the finished canvas.  `path` gains "+place" before "+resize" when some image
-    has a placement other than (w, h, 0, 0); one that shows no pixel is a FormatError, a list of another length a ValueError."""
+    has a placement other than (w, h, 0, 0); one that shows no pixel is a FormatError, a list of another length a ValueError.
 
-    def __init__(self, descs, device=0, flags=N.BATCH_DEFAULT, windows=None, output_size=None, tensor=None, rgb=False, placements=None, fill=None):
+    filter: None or "bilinear" (the default: nothing changes), "box", "hamming", "bicubic", "lanczos", or a JPGPU_FILTER_* id
+    (JPGPU_BATCH_FILTER in the flags; needs an output_size, else UnsupportedError): every resample of the batch is Pillow's
+    ``Image.resize(size, F)`` with that filter; `path` names it behind "+resize", as in "+resize:bicubic"."""
+
+    def __init__(self, descs, device=0, flags=N.BATCH_DEFAULT, windows=None, output_size=None, tensor=None, rgb=False, placements=None, fill=None,
+                 filter=None):
         self._h = C.c_void_p()
         arr = (N.ImageDesc * len(descs))(*descs)
         wins = window_structs(windows, len(descs))
@@ -204,6 +238,9 @@ class Batch:
         self.rgb = bool(rgb) or bool(flags & N.BATCH_RGB_OUTPUT)
         if rgb:
             flags |= N.BATCH_RGB_OUTPUT
+        if filter is not None:
+            flags = (flags & ~N.BATCH_FILTER(15)) | N.BATCH_FILTER(filter_id(filter))
+        self.filter = N.FILTER_NAMES[(flags >> 8) & 15] if (flags >> 8) & 15 < len(N.FILTER_NAMES) else (flags >> 8) & 15
         pls = placement_structs(placements, len(descs))
         self.fill = fill_tuple(fill)
         if pls is not None:

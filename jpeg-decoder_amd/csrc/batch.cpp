@@ -18,10 +18,12 @@ static int batch_resample_tables(jpgpu_batch *b) {
     const uint32_t n = (uint32_t)b->descs.size();
     b->rs_jobs.assign(n, ResampleJob{});
     b->rs_tab.clear();
-    b->rs_max_bands = b->rs_lds_bytes = 0;
+    b->rs_max_bands = b->rs_lds_bytes = b->rs_max_runs = 0;
+    b->rs_bpr.assign(n, 0u);
     std::map<uint64_t, std::pair<uint32_t, uint32_t>> seen;  // (in, out) -> offsets of bounds, coefficients
+    const uint32_t filter = b->filter;                       // (one per batch: the keys need not hold it)
     auto axis = [&](uint32_t in, uint32_t out, uint32_t &bo, uint32_t &ko, uint32_t &ks) {
-        ks = resample_ksize(in, out);
+        ks = resample_ksize_filtered(filter, in, out);
         const uint64_t key = ((uint64_t)in << 32) | out;
         auto it = seen.find(key);
         if (it != seen.end()) return bo = it->second.first, ko = it->second.second, true;
@@ -29,14 +31,14 @@ static int batch_resample_tables(jpgpu_batch *b) {
         if (end > 0xffffffffull) return false;
         b->rs_tab.resize(end);
         bo = (uint32_t)base, ko = (uint32_t)(base + 2u * out);
-        resample_coefficients(in, out, b->rs_tab.data() + bo, b->rs_tab.data() + ko, ks);
+        resample_coefficients_filtered(filter, in, out, b->rs_tab.data() + bo, b->rs_tab.data() + ko, ks);
         seen[key] = {bo, ko};
         return true;
     };
     // a placed batch: entries [first, first + count) of the axis (in, out) — the visible range, nothing else is tabulated
     std::map<std::array<uint32_t, 4>, std::pair<uint32_t, uint32_t>> seen_range;
     auto axis_range = [&](uint32_t in, uint32_t out, uint32_t first, uint32_t count, uint32_t &bo, uint32_t &ko, uint32_t &ks) {
-        ks = resample_ksize(in, out);
+        ks = resample_ksize_filtered(filter, in, out);
         const std::array<uint32_t, 4> key = {in, out, first, count};
         auto it = seen_range.find(key);
         if (it != seen_range.end()) return bo = it->second.first, ko = it->second.second, true;
@@ -44,7 +46,7 @@ static int batch_resample_tables(jpgpu_batch *b) {
         if (end > 0xffffffffull) return false;
         b->rs_tab.resize(end);
         bo = (uint32_t)base, ko = (uint32_t)(base + 2u * count);
-        resample_coefficients_range(in, out, first, count, b->rs_tab.data() + bo, b->rs_tab.data() + ko, ks);
+        resample_coefficients_range_filtered(filter, in, out, first, count, b->rs_tab.data() + bo, b->rs_tab.data() + ko, ks);
         seen_range[key] = {bo, ko};
         return true;
     };
@@ -78,16 +80,24 @@ static int batch_resample_tables(jpgpu_batch *b) {
             b->rs_max_bands = std::max(b->rs_max_bands, b->rs_places[i].bands);
         } else {
             if (!resample_plan(j, b->rs_tab.data())) return set_err(b->err, JPGPU_ERR_INTERNAL, "image %u: no resample plan", i);
-            b->rs_max_bands = std::max(b->rs_max_bands, j.bands);
+            // (JPGPU_RS_ROLL, read per call: 1 never, 2 / 4 / 8 every candidate with that many bands per run — the benchmark's A/B)
+            const char *knob = getenv("JPGPU_RS_ROLL");
+            const uint32_t bpr = b->rs_bpr[i] = resample_roll_bpr(j, b->rs_tab.data(), filter, knob ? (uint32_t)atoi(knob) : 0u);
+            if (bpr) b->rs_max_runs = std::max(b->rs_max_runs, (j.bands + bpr - 1u) / bpr);
+            else b->rs_max_bands = std::max(b->rs_max_bands, j.bands);
         }
         b->rs_lds_bytes = std::max(b->rs_lds_bytes, j.lds_bytes);
     }
+    const size_t roll_at = b->path.find("+roll");  // (the path names the route where any image took it; other windows may change that)
+    if (roll_at != std::string::npos) b->path.erase(roll_at);
+    if (b->rs_max_runs) b->path += "+roll";
     B_HIP(batch_wait_enqueued(b));  // (a decode still queued reads the tables)
     if (b->rs_tab.size() > b->rs_tab_cap) {
         B_HIP(hipDeviceSynchronize());
         B_HIP(grow_device(b->d_rs_tab, b->rs_tab_cap, b->rs_tab.size()));
     }
     B_HIP(hipMemcpy(b->d_rs_tab, b->rs_tab.data(), b->rs_tab.size() * sizeof(int32_t), hipMemcpyHostToDevice));
+    if (b->d_rs_bpr) B_HIP(hipMemcpy(b->d_rs_bpr, b->rs_bpr.data(), (size_t)n * sizeof(uint32_t), hipMemcpyHostToDevice));
     b->jobs_dirty = true;  // (the jobs go up with the others)
     return JPGPU_OK;
 }
@@ -109,7 +119,7 @@ static int batch_upload_tensor_jobs(jpgpu_batch *b, hipStream_t stream) {
     const uint32_t n = (uint32_t)b->descs.size();
     if (!b->h_tn_jobs && !b->h_ptn_jobs) {
         if (b->placed) B_HIP(hipHostMalloc((void **)&b->h_ptn_jobs, (size_t)n * sizeof(PlacedTensorJob), hipHostMallocDefault));
-        else B_HIP(hipHostMalloc((void **)&b->h_tn_jobs, (size_t)n * sizeof(TensorJob), hipHostMallocDefault));
+        else B_HIP(hipHostMalloc((void **)&b->h_tn_jobs, (size_t)n * 2u * sizeof(TensorJob), hipHostMallocDefault));
         B_HIP(hipEventCreateWithFlags(&b->tn_sent, hipEventDisableTiming));
     } else {
         B_HIP(hipEventSynchronize(b->tn_sent));  // (the copy before this one has read the mirror)
@@ -130,8 +140,11 @@ static int batch_upload_tensor_jobs(jpgpu_batch *b, hipStream_t stream) {
         b->h_tn_jobs[i].r = b->rs_jobs[i];
         b->h_tn_jobs[i].plane = b->rs_w * b->rs_h;
         b->h_tn_jobs[i].flip = b->tn_flips[i] ? 1u : 0u;
+        if (!b->rs_max_runs) continue;
+        b->h_tn_jobs[n + i] = b->h_tn_jobs[i];               // (the run launch's: the real job)
+        if (b->rs_bpr[i]) b->h_tn_jobs[i].r.bands = 0u;  // (the band launch's: no band of this image)
     }
-    B_HIP(hipMemcpyAsync(b->d_tn_jobs, b->h_tn_jobs, (size_t)n * sizeof(TensorJob), hipMemcpyHostToDevice, stream));
+    B_HIP(hipMemcpyAsync(b->d_tn_jobs, b->h_tn_jobs, (size_t)n * (b->rs_max_runs ? 2u : 1u) * sizeof(TensorJob), hipMemcpyHostToDevice, stream));
     B_HIP(hipEventRecord(b->tn_sent, stream));
     b->tn_dirty = false;
     return JPGPU_OK;
@@ -209,6 +222,12 @@ static int batch_refresh_jobs(jpgpu_batch *b, hipStream_t stream = nullptr) {
             std::vector<PlacedJob> pj(n);
             for (uint32_t i = 0; i < n; i++) pj[i].r = b->rs_jobs[i], pj[i].p = b->rs_places[i];
             B_HIP(hipMemcpy(b->d_pl_jobs, pj.data(), (size_t)n * sizeof(PlacedJob), hipMemcpyHostToDevice));
+        } else if (b->rs_max_runs) {  // (band launch: images in runs have no band; run launch: the real jobs)
+            std::vector<ResampleJob> both(b->rs_jobs);
+            both.insert(both.end(), b->rs_jobs.begin(), b->rs_jobs.end());
+            for (uint32_t i = 0; i < n; i++)
+                if (b->rs_bpr[i]) both[i].bands = 0u;
+            B_HIP(hipMemcpy(b->d_rs_jobs, both.data(), (size_t)n * 2u * sizeof(ResampleJob), hipMemcpyHostToDevice));
         } else {
             B_HIP(hipMemcpy(b->d_rs_jobs, b->rs_jobs.data(), (size_t)n * sizeof(ResampleJob), hipMemcpyHostToDevice));
         }
@@ -239,6 +258,12 @@ static int batch_create(int device, const jpgpu_image_desc *descs, const jpgpu_w
     const bool resized = rs_w != 0 || rs_h != 0;
     if (resized && (rs_w == 0 || rs_h == 0 || rs_w > RS_MAX_OUT || rs_h > RS_MAX_OUT))
         return set_err(b->err, JPGPU_ERR_FORMAT, "output size %ux%u: width and height must be 1..%u", rs_w, rs_h, RS_MAX_OUT);
+    const uint32_t filter = (flags >> 8) & 15u;  // JPGPU_BATCH_FILTER(f): 0 is BILINEAR, so flags without the bits mean what they meant
+    if (filter >= RS_FILTERS) return set_err(b->err, JPGPU_ERR_FORMAT, "resample filter %u: the ids are 0..%u (JPGPU_FILTER_*)", filter, RS_FILTERS - 1u);
+    if (filter && !resized)
+        return set_err(b->err, JPGPU_ERR_UNSUPPORTED, "a resample filter (%s) needs an output size (jpgpu_batch_create_resized / _create_tensor / _create_placed)",
+                       resample_filter_name(filter));
+    b->filter = filter;
     const bool rgb = (flags & JPGPU_BATCH_RGB_OUTPUT) != 0;  // (every image gives three channels: the resample converts gray and CMYK)
     if (rgb && !resized)
         return set_err(b->err, JPGPU_ERR_UNSUPPORTED, "JPGPU_BATCH_RGB_OUTPUT needs an output size (jpgpu_batch_create_resized / _create_tensor)");
@@ -374,6 +399,7 @@ static int batch_create(int device, const jpgpu_image_desc *descs, const jpgpu_w
     if (rgb) b->path += "+rgb";
     if (b->placed) b->path += "+place";
     if (resized) b->path += "+resize";
+    if (filter) b->path += std::string(":") + resample_filter_name(filter);
     if (tensor) b->path += "+tensor";
     const size_t full = arena_layout(b->out_full_len);  // (what the whole images take)
     if (!(flags & JPGPU_BATCH_EXTERNAL_BUFFERS)) {
@@ -389,7 +415,7 @@ static int batch_create(int device, const jpgpu_image_desc *descs, const jpgpu_w
         B_HIP(hipMalloc((void **)&b->d_pix, b->pix_cap));
         if (tensor) {  // (the table of four channels: every image looks up its own first ncomp rows)
             if (b->placed) B_HIP(hipMalloc((void **)&b->d_ptn_jobs, (size_t)n_images * sizeof(PlacedTensorJob)));
-            else B_HIP(hipMalloc((void **)&b->d_tn_jobs, (size_t)n_images * sizeof(TensorJob)));
+            else B_HIP(hipMalloc((void **)&b->d_tn_jobs, (size_t)n_images * 2u * sizeof(TensorJob)));
             B_HIP(hipMalloc(&b->d_tn_table, TN_TABLE_MAX));
             std::vector<uint32_t> table(TN_TABLE_MAX / 4u, 0u);
             uint32_t nc_max = rgb ? 3u : 1u;
@@ -399,8 +425,9 @@ static int batch_create(int device, const jpgpu_image_desc *descs, const jpgpu_w
         } else if (b->placed) {
             B_HIP(hipMalloc((void **)&b->d_pl_jobs, (size_t)n_images * sizeof(PlacedJob)));
         } else {
-            B_HIP(hipMalloc((void **)&b->d_rs_jobs, (size_t)n_images * sizeof(ResampleJob)));
+            B_HIP(hipMalloc((void **)&b->d_rs_jobs, (size_t)n_images * 2u * sizeof(ResampleJob)));
         }
+        if (!b->placed) B_HIP(hipMalloc((void **)&b->d_rs_bpr, (size_t)n_images * sizeof(uint32_t)));
     }
     if (!b->generic_ids.empty()) B_HIP(hipMalloc((void **)&b->d_planes, b->plane_bytes_total));
     for (FusedPlan &fp : b->fused) {
@@ -482,6 +509,7 @@ void jpgpu_batch_destroy(jpgpu_batch *b) {
         if (b->d_planes) hipFree(b->d_planes);
         if (b->d_pix) hipFree(b->d_pix);
         if (b->d_rs_jobs) hipFree(b->d_rs_jobs);
+        if (b->d_rs_bpr) hipFree(b->d_rs_bpr);
         if (b->d_tn_jobs) hipFree(b->d_tn_jobs);
         if (b->d_pl_jobs) hipFree(b->d_pl_jobs);
         if (b->d_ptn_jobs) hipFree(b->d_ptn_jobs);
@@ -973,6 +1001,11 @@ int jpgpu_batch_decode(jpgpu_batch *b, void *hip_stream) {
                                       (b->flags & JPGPU_BATCH_RGB_OUTPUT) != 0));
     else if (b->rs_w)  // (an output size: every image's pixels, wherever the launches above left them in the intermediate arena)
         B_HIP(launch_resample_band(b->d_rs_jobs, b->d_rs_tab, (uint32_t)b->descs.size(), b->rs_max_bands, b->rs_lds_bytes, s, (b->flags & JPGPU_BATCH_RGB_OUTPUT) != 0));
+    if (b->rs_max_runs && !b->placed) {  // (the images whose bands go in runs: their own launch, beside the band launch above)
+        const uint32_t n_rs = (uint32_t)b->descs.size();
+        if (b->tn_es) B_HIP(launch_resample_tensor_run(b->d_tn_jobs + n_rs, b->d_rs_tab, b->d_tn_table, b->d_rs_bpr, b->tn_es, n_rs, b->rs_max_runs, b->rs_lds_bytes, s));
+        else B_HIP(launch_resample_run(b->d_rs_jobs + n_rs, b->d_rs_tab, b->d_rs_bpr, n_rs, b->rs_max_runs, b->rs_lds_bytes, s));
+    }
     if (b->phase_events_valid) B_HIP(hipEventRecord(b->ev_phase[5], s));
     B_HIP(batch_mark_enqueued(b, s));
     return JPGPU_OK;

@@ -123,6 +123,7 @@ struct jpgpu_batch {
     // out_bytes) then holds rs_h x rs_w x ncomp bytes per image, and every pixel kernel above writes what it always writes — the window's
     // or the whole image's pixels — into an intermediate arena the batch owns (d_pix, pix_off, pix_len), which one more launch resamples.
     uint32_t rs_w = 0, rs_h = 0;
+    uint32_t filter = 0;  // the resample filter (JPGPU_BATCH_FILTER bits of the flags): every table of the batch is made with it
     std::vector<size_t> pix_off, pix_len;
     size_t pix_bytes = 0, pix_cap = 0;
     uint8_t *d_pix = nullptr;
@@ -132,6 +133,13 @@ struct jpgpu_batch {
     int32_t *d_rs_tab = nullptr;
     size_t rs_tab_cap = 0;             // int32 words behind d_rs_tab
     uint32_t rs_max_bands = 0, rs_lds_bytes = 0;
+    // Runs of bands (resample_band.hpp): rs_bpr[i] != 0 — image i's bands go, rs_bpr[i] at a time, to the workgroups of a
+    // second launch (resample_run_kernel / resample_tensor_run_kernel) and the band launch sees the image with no band.  The device job
+    // arrays hold 2 n entries: [0, n) for the band launch, [n, 2 n) the images' real jobs for the run launch.  rs_max_bands is over the
+    // images that keep their bands, rs_max_runs over the others (0: no run launch; never with placements or BILINEAR).
+    std::vector<uint32_t> rs_bpr;
+    uint32_t *d_rs_bpr = nullptr;
+    uint32_t rs_max_runs = 0;
     // A tensor output (jpgpu_batch_create_tensor, tensor_band.hpp; tn_es == 0: none): an output size whose resample launch writes the
     // normalised CHW tensor of every image instead of its resized pixels.  The output arena holds ncomp x rs_h x rs_w elements per image;
     // the planner, the tables and rs_jobs are the output size's, the device jobs are TensorJobs (rs_jobs[i] + the image's flip).

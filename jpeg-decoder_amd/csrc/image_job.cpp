@@ -205,6 +205,24 @@ int jpgpu_resample_coefficients_range(uint32_t in_size, uint32_t out_size, uint3
     return JPGPU_OK;
 }
 
+// the same two under a filter (JPGPU_FILTER_*; filter 0 is the two above)
+int jpgpu_resample_coefficients_filtered(uint32_t filter, uint32_t in_size, uint32_t out_size, int32_t *bounds, int32_t *coefs, uint32_t *ksize) {
+    if (filter >= jpgpu::RS_FILTERS) return JPGPU_ERR_FORMAT;
+    if (in_size == 0 || out_size == 0 || in_size > 65535u || out_size > 65535u || !ksize || (!bounds) != (!coefs)) return JPGPU_ERR_FORMAT;
+    *ksize = jpgpu::resample_ksize_filtered(filter, in_size, out_size);
+    if (bounds) jpgpu::resample_coefficients_filtered(filter, in_size, out_size, bounds, coefs, *ksize);
+    return JPGPU_OK;
+}
+int jpgpu_resample_coefficients_range_filtered(uint32_t filter, uint32_t in_size, uint32_t out_size, uint32_t first, uint32_t count, int32_t *bounds,
+                                               int32_t *coefs, uint32_t *ksize) {
+    if (filter >= jpgpu::RS_FILTERS) return JPGPU_ERR_FORMAT;
+    if (in_size == 0 || out_size == 0 || in_size > 65535u || out_size > 65535u || !ksize || (!bounds) != (!coefs)) return JPGPU_ERR_FORMAT;
+    if (first > out_size || count > out_size - first) return JPGPU_ERR_FORMAT;
+    *ksize = jpgpu::resample_ksize_filtered(filter, in_size, out_size);
+    if (bounds) jpgpu::resample_coefficients_range_filtered(filter, in_size, out_size, first, count, bounds, coefs, *ksize);
+    return JPGPU_OK;
+}
+
 // the placement rules (placed_band.hpp; the pipeline places every image with the same function)
 int jpgpu_fit_placement(const jpgpu_fit *fit, uint32_t src_w, uint32_t src_h, uint32_t out_w, uint32_t out_h, jpgpu_placement *out) {
     if (!fit || !out || fit->reserved != 0) return JPGPU_ERR_FORMAT;

@@ -261,6 +261,7 @@ struct SubBatch {
     bool tensor = false;              // the tensor format the batch was created with (jpgpu_pipeline_set_tensor_output), if any
     jpgpu_tensor_format tn{};
     bool rgb = false;                 // created with JPGPU_BATCH_RGB_OUTPUT (jpgpu_pipeline_set_rgb_output)
+    uint32_t filter = 0;              // created with JPGPU_BATCH_FILTER(filter) (jpgpu_pipeline_set_filter)
     std::vector<uint8_t> flips;       // a tensor batch: the flip of every image as the batch holds it (jpgpu_batch_set_flips)
     bool fit_on = false;              // created with placements under this rule (jpgpu_pipeline_set_fit)
     jpgpu_fit fit{};
@@ -281,6 +282,7 @@ struct SubBatch {
         rs_w = rs_h = 0;
         tensor = false;
         rgb = false;
+        filter = 0;
         flips.clear();
         fit_on = false;
         fit = jpgpu_fit{};
@@ -328,6 +330,7 @@ struct jpgpu_pipeline {
     uint16_t rs_w = 0, rs_h = 0;    // jpgpu_pipeline_set_output_size (0 x 0: none)
     bool tensor = false;            // jpgpu_pipeline_set_tensor_output
     bool rgb = false;               // jpgpu_pipeline_set_rgb_output
+    uint32_t filter = 0;            // jpgpu_pipeline_set_filter (JPGPU_FILTER_*; 0: bilinear)
     bool fit_on = false;            // jpgpu_pipeline_set_fit (a rule other than stretch)
     jpgpu_fit fit{};
     jpgpu_tensor_format tn{};
@@ -651,6 +654,7 @@ int jpgpu_pipeline_decode_augmented(jpgpu_pipeline *p, const uint8_t *const *dat
     // (a tensor output needs an output size, flips a tensor output: refused before anything is decoded)
     if (p && p->tensor && !p->rs_w) return jpgpu::set_err(p->err, JPGPU_ERR_FORMAT, "jpgpu_pipeline_decode: a tensor output needs an output size (jpgpu_pipeline_set_output_size)");
     if (p && p->rgb && !p->rs_w) return jpgpu::set_err(p->err, JPGPU_ERR_FORMAT, "jpgpu_pipeline_decode: RGB output needs an output size (jpgpu_pipeline_set_output_size)");
+    if (p && p->filter && !p->rs_w) return jpgpu::set_err(p->err, JPGPU_ERR_FORMAT, "jpgpu_pipeline_decode: a resample filter needs an output size (jpgpu_pipeline_set_output_size)");
     if (p && p->fit_on && !p->rs_w) return jpgpu::set_err(p->err, JPGPU_ERR_FORMAT, "jpgpu_pipeline_decode: a fit needs an output size (jpgpu_pipeline_set_output_size)");
     if (p && flips && !p->tensor) return jpgpu::set_err(p->err, JPGPU_ERR_FORMAT, "jpgpu_pipeline_decode_augmented: flips need a tensor output (jpgpu_pipeline_set_tensor_output)");
     if (p && !p->children.empty()) return (n && (!data || !len)) ? JPGPU_ERR_FORMAT : multi_decode(p, data, len, windows, flips, n, flags);
@@ -891,6 +895,7 @@ int jpgpu_pipeline_decode_augmented(jpgpu_pipeline *p, const uint8_t *const *dat
         bool reuse = sb.batch && descs.size() == sb.descs.size() && sb.compact == compact && (sb.h_coef != nullptr) == staged && sb.rs_w == p->rs_w && sb.rs_h == p->rs_h &&
                      sb.rgb == p->rgb && sb.tensor == p->tensor && (!p->tensor || memcmp(&sb.tn, &p->tn, sizeof(jpgpu_tensor_format)) == 0);  // (... or another tensor format)
         // (... or another fit: the batch is placed or not, and holds the fill, for its lifetime)
+        reuse = reuse && sb.filter == p->filter;  // (... or another filter: other tables throughout)
         reuse = reuse && sb.fit_on == p->fit_on && (!p->fit_on || memcmp(&sb.fit, &p->fit, sizeof(jpgpu_fit)) == 0);
         const bool same_pls = pls.size() == sb.pls.size() && (pls.empty() || memcmp(pls.data(), sb.pls.data(), pls.size() * sizeof(jpgpu_placement)) == 0);
         for (size_t k = 0; reuse && k < descs.size(); k++) reuse = same_geometry(descs[k], sb.descs[k]);
@@ -911,7 +916,8 @@ int jpgpu_pipeline_decode_augmented(jpgpu_pipeline *p, const uint8_t *const *dat
         }
         if (!reuse) {
             sb.drop();
-            const uint32_t bf = p->rgb ? JPGPU_BATCH_RGB_OUTPUT : JPGPU_BATCH_DEFAULT;  // (every image three channels: the batch's resample converts)
+            const uint32_t bf = (p->rgb ? JPGPU_BATCH_RGB_OUTPUT : JPGPU_BATCH_DEFAULT) |  // (every image three channels: the batch's resample converts)
+                                JPGPU_BATCH_FILTER(p->filter);                             // (0 without an output size: checked above)
             rc = p->fit_on ? jpgpu_batch_create_placed(p->device, descs.data(), wins.empty() ? nullptr : wins.data(), pls.data(), p->fit.fill, p->rs_w, p->rs_h,
                                                        p->tensor ? &p->tn : nullptr, (uint32_t)descs.size(), bf, &sb.batch)
                  : p->tensor ? jpgpu_batch_create_tensor(p->device, descs.data(), wins.empty() ? nullptr : wins.data(), p->rs_w, p->rs_h, &p->tn, (uint32_t)descs.size(), bf, &sb.batch)
@@ -935,6 +941,7 @@ int jpgpu_pipeline_decode_augmented(jpgpu_pipeline *p, const uint8_t *const *dat
             sb.rs_w = p->rs_w, sb.rs_h = p->rs_h;
             sb.tensor = p->tensor, sb.tn = p->tn;
             sb.rgb = p->rgb;
+            sb.filter = p->filter;
             sb.fit_on = p->fit_on, sb.fit = p->fit, sb.pls = pls;
             sb.flips.assign(descs.size(), 0);
             sb.compact = compact;
@@ -1505,6 +1512,13 @@ int jpgpu_pipeline_image_placement(const jpgpu_pipeline *p, uint32_t i, jpgpu_pl
     MULTI(p, i, jpgpu_pipeline_image_placement(c, ci, out), JPGPU_ERR_FORMAT)
     if (!p || i >= p->n || !out || i >= p->places.size() || p->places[i].rw == 0 || p->places[i].rh == 0) return JPGPU_ERR_FORMAT;
     *out = p->places[i];
+    return JPGPU_OK;
+}
+int jpgpu_pipeline_set_filter(jpgpu_pipeline *p, uint32_t filter) {
+    if (!p) return JPGPU_ERR_FORMAT;
+    if (filter > JPGPU_FILTER_LANCZOS) return jpgpu::set_err(p->err, JPGPU_ERR_FORMAT, "resample filter %u: the ids are 0..4 (JPGPU_FILTER_*)", filter);
+    for (jpgpu_pipeline *c : p->children) jpgpu_pipeline_set_filter(c, filter);
+    p->filter = filter;
     return JPGPU_OK;
 }
 int jpgpu_pipeline_set_rgb_output(jpgpu_pipeline *p, int on) {

@@ -29,44 +29,7 @@ namespace jpgpu {
 // Entries [first, first + count) of the tables resample_coefficients(in_size, out_size, ...) gives: bounds[2 i], bounds[2 i + 1] and
 // coefs[i * ksize + x] belong to output index first + i.  The statements are resample_coefficients', entry by entry.
 inline void resample_coefficients_range(uint32_t in_size, uint32_t out_size, uint32_t first, uint32_t count, int32_t *bounds, int32_t *coefs, uint32_t ksize) {
-    const double scale = (double)in_size / (double)out_size;
-    const double fs = scale < 1.0 ? 1.0 : scale;
-    const double support = fs;
-    const double ss = 1.0 / fs;
-    for (uint32_t i = 0; i < count; i++) {
-        const uint32_t xx = first + i;
-        const double center = ((double)xx + 0.5) * scale;
-        int32_t xmin = (int32_t)(center - support + 0.5);
-        if (xmin < 0) xmin = 0;
-        int32_t xmax = (int32_t)(center + support + 0.5);
-        if (xmax > (int32_t)in_size) xmax = (int32_t)in_size;
-        const int32_t n = xmax - xmin;
-        int32_t *k = coefs + (size_t)i * ksize;
-        double ww = 0.0;
-        for (int32_t x = 0; x < n; x++) {
-            double a = (double)(x + xmin) - center;
-            a = a + 0.5;
-            a = a * ss;
-            if (a < 0.0) a = -a;
-            const double w = a < 1.0 ? 1.0 - a : 0.0;
-            ww = ww + w;
-        }
-        for (int32_t x = 0; x < (int32_t)ksize; x++) {
-            if (x >= n) {
-                k[x] = 0;
-                continue;
-            }
-            double a = (double)(x + xmin) - center;
-            a = a + 0.5;
-            a = a * ss;
-            if (a < 0.0) a = -a;
-            const double w = a < 1.0 ? 1.0 - a : 0.0;
-            double v = ww != 0.0 ? w / ww : w;
-            v = v * (double)(1 << RS_PRECISION_BITS);
-            k[x] = (int32_t)(v + 0.5);
-        }
-        bounds[2 * i] = xmin, bounds[2 * i + 1] = n;
-    }
+    resample_coefficients_range_filtered(RS_FILTER_BILINEAR, in_size, out_size, first, count, bounds, coefs, ksize);
 }
 
 // The visible range of one axis: a resample of `r` entries laid at `at` in a canvas of `out`.  False when nothing shows.

@@ -184,4 +184,101 @@ hipError_t launch_resample_tensor(const TensorJob *d_jobs, const int32_t *d_tab,
     return hipGetLastError();
 }
 
+// ---- Runs of bands: new kernels beside the band kernels above, which stay what they are. ----
+// A workgroup owns the bands [band0, band1) of one image, every one of a single chunk.  The first band is the band kernels': horizontal
+// pass of its source rows [s0, s1) into LDS rows 0.., barrier, vertical pass.  For every further band the rows it shares with the band
+// before, [s0(b), s1(b - 1)), already lie in LDS: they move down to where this band expects them (row s - s0(b); RBand::roll_*: read,
+// barrier, write, barrier per slab), and only the new rows [max(s1(b - 1), s0(b)), s1(b)) go through the horizontal pass.  The vertical
+// pass (`vstore(band)`: RBand::vstore / TBand<E>::vstore) runs with the band index, unchanged.  LDS: the plan's lds_bytes, as ever.
+template <uint32_t KIND, class V>
+static __device__ __forceinline__ void resample_run_body(const ResampleJob &j, const JP_GLOBAL int32_t *tab, uint32_t band0, uint32_t band1, uint32_t tid,
+                                                         uint8_t *lds, const V &vstore) {
+    for (uint32_t band = band0; band < band1; band++) {  // (uniform)
+        if (band == band0) {
+            uint32_t r0, r1, s0, s1;
+            RBand::rows_of(j, tab, band, r0, r1, s0, s1);
+            RBand::hpass_rows_of<KIND>(j, tab, s0, s1 - s0, 0u, tid, lds);
+        } else {
+            uint32_t shift, keep, n0, s0, s1;
+            RBand::roll_of(j, tab, band, shift, keep, n0, s0, s1);
+            __syncthreads();  // (the vertical pass of the band before has read its rows)
+            if (shift != 0u && keep != 0u) {
+                const uint32_t slabs = RBand::roll_slabs(j, keep);
+                for (uint32_t slab = 0; slab < slabs; slab++) {
+                    uint32_t reg[RS_ROLL_DW];
+                    RBand::roll_read(j, shift, keep, slab, tid, lds, reg);
+                    __syncthreads();
+                    RBand::roll_write(j, keep, slab, tid, lds, reg);
+                    __syncthreads();
+                }
+            }
+            if (s1 > n0) RBand::hpass_rows_of<KIND>(j, tab, n0, s1 - n0, n0 - s0, tid, lds);
+        }
+        __syncthreads();
+        vstore(band);
+    }
+}
+
+// The grid is the band kernels', numbered for the XCDs, over runs: image `image` takes XCD image % 8, its runs are consecutive slots.
+__global__ __launch_bounds__(RS_NT, 4) void resample_run_kernel(const ResampleJob *__restrict__ jobs, const int32_t *__restrict__ tab_, const uint32_t *__restrict__ bprs,
+                                                             uint32_t max_runs, uint32_t n_images) {
+    extern __shared__ __attribute__((aligned(16))) uint8_t lds_raw[];
+    const uint32_t xcd = blockIdx.x & 7u, slot = blockIdx.x >> 3, image = (slot / max_runs) * 8u + xcd, run = slot % max_runs;
+    if (image >= n_images) return;
+    const uint32_t bpr = bprs[image];
+    if (bpr == 0u) return;  // (uniform: the image keeps its bands)
+    const ResampleJob j = jobs[image];
+    const uint32_t band0 = run * bpr, band1 = min(band0 + bpr, j.bands), tid = threadIdx.x;
+    if (band0 >= j.bands) return;  // (uniform)
+    const JP_GLOBAL int32_t *tab = (const JP_GLOBAL int32_t *)tab_;
+    auto vstore = [&](uint32_t band) { RBand::vstore(j, tab, band, tid, lds_raw); };
+    if (j.src_nc == 0u) resample_run_body<0u>(j, tab, band0, band1, tid, lds_raw, vstore);  // (uniform; RGB output: the converting passes)
+    else if (j.src_nc == 1u) resample_run_body<1u>(j, tab, band0, band1, tid, lds_raw, vstore);
+    else resample_run_body<4u>(j, tab, band0, band1, tid, lds_raw, vstore);
+}
+
+template <class E>
+__global__ __launch_bounds__(RS_NT, 4) void resample_tensor_run_kernel(const TensorJob *__restrict__ jobs, const int32_t *__restrict__ tab_,
+                                                                    const uint32_t *__restrict__ ttab_, const uint32_t *__restrict__ bprs, uint32_t max_runs,
+                                                                    uint32_t n_images) {
+    extern __shared__ __attribute__((aligned(16))) uint8_t lds_raw[];
+    const uint32_t xcd = blockIdx.x & 7u, slot = blockIdx.x >> 3, image = (slot / max_runs) * 8u + xcd, run = slot % max_runs;
+    if (image >= n_images) return;
+    const uint32_t bpr = bprs[image];
+    if (bpr == 0u) return;  // (uniform)
+    const TensorJob t = jobs[image];
+    const uint32_t band0 = run * bpr, band1 = min(band0 + bpr, t.r.bands), tid = threadIdx.x;
+    if (band0 >= t.r.bands) return;  // (uniform)
+    const JP_GLOBAL int32_t *tab = (const JP_GLOBAL int32_t *)tab_;
+    TBand<E>::load_table(t, (const JP_GLOBAL uint32_t *)ttab_, tid, lds_raw);  // (behind the rows: the move never reaches it)
+    auto vstore = [&](uint32_t band) { TBand<E>::vstore(t, tab, band, tid, lds_raw); };
+    if (t.r.src_nc == 0u) resample_run_body<0u>(t.r, tab, band0, band1, tid, lds_raw, vstore);
+    else if (t.r.src_nc == 1u) resample_run_body<1u>(t.r, tab, band0, band1, tid, lds_raw, vstore);
+    else resample_run_body<4u>(t.r, tab, band0, band1, tid, lds_raw, vstore);
+}
+
+hipError_t launch_resample_run(const ResampleJob *d_jobs, const int32_t *d_tab, const uint32_t *d_bpr, uint32_t n_images, uint32_t max_runs, uint32_t lds_bytes,
+                               hipStream_t stream) {
+    if (n_images == 0 || max_runs == 0) return hipSuccess;
+    if (lds_bytes > RS_MAX_LDS) return hipErrorInvalidValue;
+    const uint64_t wgs = (((uint64_t)n_images + 7u) / 8u) * 8u * max_runs;
+    if (wgs > 0x7fffffffull) return hipErrorInvalidValue;
+    resample_run_kernel<<<dim3((uint32_t)wgs), dim3(RS_NT), lds_bytes, stream>>>(d_jobs, d_tab, d_bpr, max_runs, n_images);
+    return hipGetLastError();
+}
+
+hipError_t launch_resample_tensor_run(const TensorJob *d_jobs, const int32_t *d_tab, const void *d_ttab, const uint32_t *d_bpr, uint32_t elem_bytes, uint32_t n_images,
+                                      uint32_t max_runs, uint32_t lds_bytes, hipStream_t stream) {
+    if (n_images == 0 || max_runs == 0) return hipSuccess;
+    if (lds_bytes > RS_MAX_LDS || (elem_bytes != 2u && elem_bytes != 4u)) return hipErrorInvalidValue;
+    const uint64_t wgs = (((uint64_t)n_images + 7u) / 8u) * 8u * max_runs;
+    if (wgs > 0x7fffffffull) return hipErrorInvalidValue;
+    const uint32_t lds = ((lds_bytes + 15u) & ~15u) + 4u * 256u * elem_bytes;  // the rows, then the table
+    if (elem_bytes == 4u)
+        resample_tensor_run_kernel<uint32_t><<<dim3((uint32_t)wgs), dim3(RS_NT), lds, stream>>>(d_jobs, d_tab, (const uint32_t *)d_ttab, d_bpr, max_runs, n_images);
+    else
+        resample_tensor_run_kernel<uint16_t><<<dim3((uint32_t)wgs), dim3(RS_NT), lds, stream>>>(d_jobs, d_tab, (const uint32_t *)d_ttab, d_bpr, max_runs, n_images);
+    return hipGetLastError();
+}
+
 }  // namespace jpgpu

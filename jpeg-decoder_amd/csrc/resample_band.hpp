@@ -23,6 +23,7 @@
 //      horizontal pass (RBand::hpass_walk<1> / hpass_cmyk) converts the source pixels and leaves the three-channel rows in LDS that 2.
 //      leaves for a three-channel source — 1., 3. and 4. run unchanged with nc = 3.
 #pragma once
+#include <math.h>
 #include <stddef.h>
 #include <stdint.h>
 
@@ -41,37 +42,101 @@ constexpr uint32_t RS_MAX_LDS = 32u * 1024u;  // 5 workgroups share a CU's 160 k
 constexpr uint32_t RS_MAX_OUT = 2048;         // largest output width / height
 constexpr uint32_t RS_PRECISION_BITS = 22;
 
-// ksize of an axis: ceil(max(in / out, 1)) * 2 + 1
-inline uint32_t resample_ksize(uint32_t in_size, uint32_t out_size) {
-    const double scale = (double)in_size / (double)out_size;
-    const double fs = scale < 1.0 ? 1.0 : scale;
-    uint32_t c = (uint32_t)fs;
-    if ((double)c < fs) c++;
-    return c * 2u + 1u;
+// The filters of DESIGN.md §4.15 (JPGPU_FILTER_* of include/jpgpu.h): Pillow's BILINEAR, BOX, HAMMING, BICUBIC and LANCZOS.
+constexpr uint32_t RS_FILTER_BILINEAR = 0, RS_FILTER_BOX = 1, RS_FILTER_HAMMING = 2, RS_FILTER_BICUBIC = 3, RS_FILTER_LANCZOS = 4, RS_FILTERS = 5;
+inline double resample_filter_support(uint32_t filter) {
+    return filter == RS_FILTER_BOX ? 0.5 : filter == RS_FILTER_BICUBIC ? 2.0 : filter == RS_FILTER_LANCZOS ? 3.0 : 1.0;
+}
+inline const char *resample_filter_name(uint32_t filter) {
+    static const char *const names[RS_FILTERS] = {"bilinear", "box", "hamming", "bicubic", "lanczos"};
+    return filter < RS_FILTERS ? names[filter] : "?";
+}
+// sin(pi x) / (pi x), one operation per statement
+inline double resample_sinc(double x) {
+    if (x == 0.0) return 1.0;
+    x = x * M_PI;
+    const double s = sin(x);
+    return s / x;
+}
+// The filter's weight at the SIGNED argument x: IEEE double, libm's sin and cos, one operation per statement (nothing for a compiler
+// to contract into an FMA) in the order of the statement in DESIGN.md §4.15.
+inline double resample_filter_weight(uint32_t filter, double x) {
+    if (filter == RS_FILTER_BOX) return (x > -0.5 && x <= 0.5) ? 1.0 : 0.0;
+    if (filter == RS_FILTER_LANCZOS) {
+        if (!(-3.0 <= x && x < 3.0)) return 0.0;
+        const double s1 = resample_sinc(x);
+        const double x3 = x / 3.0;
+        const double s3 = resample_sinc(x3);
+        return s1 * s3;
+    }
+    if (x < 0.0) x = -x;
+    if (filter == RS_FILTER_HAMMING) {
+        if (x == 0.0) return 1.0;
+        if (x >= 1.0) return 0.0;
+        x = x * M_PI;
+        const double s = sin(x);
+        const double q = s / x;
+        const double c = cos(x);
+        double h = (double)0.46f * c;  // (the two constants are float literals promoted to double)
+        h = (double)0.54f + h;
+        return q * h;
+    }
+    if (filter == RS_FILTER_BICUBIC) {  // a = -0.5
+        if (x < 1.0) {                  // ((a + 2) x - (a + 3)) x x + 1
+            double v = 1.5 * x;
+            v = v - 2.5;
+            v = v * x;
+            v = v * x;
+            return v + 1.0;
+        }
+        if (x < 2.0) {  // (((x - 5) x + 8) x - 4) a
+            double v = x - 5.0;
+            v = v * x;
+            v = v + 8.0;
+            v = v * x;
+            v = v - 4.0;
+            return v * -0.5;
+        }
+        return 0.0;
+    }
+    return x < 1.0 ? 1.0 - x : 0.0;
 }
 
-// The tables of one axis: bounds[2 xx] = xmin, bounds[2 xx + 1] = n, coefs[xx * ksize + x] = k[x] (zero beyond n).  IEEE double, the
-// operations in the order of the statement in DESIGN.md §4.10 (one operation per statement: nothing for a compiler to contract).
-inline void resample_coefficients(uint32_t in_size, uint32_t out_size, int32_t *bounds, int32_t *coefs, uint32_t ksize) {
+// ksize of an axis: ceil(S_F * max(in / out, 1)) * 2 + 1
+inline uint32_t resample_ksize_filtered(uint32_t filter, uint32_t in_size, uint32_t out_size) {
     const double scale = (double)in_size / (double)out_size;
     const double fs = scale < 1.0 ? 1.0 : scale;
-    const double support = fs;
+    const double support = resample_filter_support(filter) * fs;
+    uint32_t c = (uint32_t)support;
+    if ((double)c < support) c++;
+    return c * 2u + 1u;
+}
+inline uint32_t resample_ksize(uint32_t in_size, uint32_t out_size) { return resample_ksize_filtered(RS_FILTER_BILINEAR, in_size, out_size); }
+
+// Entries [first, first + count) of the tables of one axis under a filter: bounds[2 i] = xmin, bounds[2 i + 1] = n,
+// coefs[i * ksize + x] = k[x] (zero beyond n) belong to output index first + i.  IEEE double, the operations in the order of the
+// statement in DESIGN.md §4.10 / §4.15 (one operation per statement: nothing for a compiler to contract).  Weights may be negative.
+inline void resample_coefficients_range_filtered(uint32_t filter, uint32_t in_size, uint32_t out_size, uint32_t first, uint32_t count, int32_t *bounds,
+                                                 int32_t *coefs, uint32_t ksize) {
+    const double scale = (double)in_size / (double)out_size;
+    const double fs = scale < 1.0 ? 1.0 : scale;
+    const double support = resample_filter_support(filter) * fs;
     const double ss = 1.0 / fs;
-    for (uint32_t xx = 0; xx < out_size; xx++) {
+    for (uint32_t i = 0; i < count; i++) {
+        const uint32_t xx = first + i;
         const double center = ((double)xx + 0.5) * scale;
         int32_t xmin = (int32_t)(center - support + 0.5);
         if (xmin < 0) xmin = 0;
         int32_t xmax = (int32_t)(center + support + 0.5);
         if (xmax > (int32_t)in_size) xmax = (int32_t)in_size;
         const int32_t n = xmax - xmin;
-        int32_t *k = coefs + (size_t)xx * ksize;
+        int32_t *k = coefs + (size_t)i * ksize;
         double ww = 0.0;
         for (int32_t x = 0; x < n; x++) {
             double a = (double)(x + xmin) - center;
             a = a + 0.5;
             a = a * ss;
-            if (a < 0.0) a = -a;
-            const double w = a < 1.0 ? 1.0 - a : 0.0;
+            const double w = resample_filter_weight(filter, a);
             ww = ww + w;
         }
         for (int32_t x = 0; x < (int32_t)ksize; x++) {
@@ -82,14 +147,20 @@ inline void resample_coefficients(uint32_t in_size, uint32_t out_size, int32_t *
             double a = (double)(x + xmin) - center;
             a = a + 0.5;
             a = a * ss;
-            if (a < 0.0) a = -a;
-            const double w = a < 1.0 ? 1.0 - a : 0.0;
+            const double w = resample_filter_weight(filter, a);
             double v = ww != 0.0 ? w / ww : w;
             v = v * (double)(1 << RS_PRECISION_BITS);
-            k[x] = (int32_t)(v + 0.5);
+            k[x] = v < 0.0 ? (int32_t)(-0.5 + v) : (int32_t)(0.5 + v);
         }
-        bounds[2 * xx] = xmin, bounds[2 * xx + 1] = n;
+        bounds[2 * i] = xmin, bounds[2 * i + 1] = n;
     }
+}
+inline void resample_coefficients_filtered(uint32_t filter, uint32_t in_size, uint32_t out_size, int32_t *bounds, int32_t *coefs, uint32_t ksize) {
+    resample_coefficients_range_filtered(filter, in_size, out_size, 0u, out_size, bounds, coefs, ksize);
+}
+// The tables of one axis under BILINEAR (§4.10): filter 0 of the above.
+inline void resample_coefficients(uint32_t in_size, uint32_t out_size, int32_t *bounds, int32_t *coefs, uint32_t ksize) {
+    resample_coefficients_range_filtered(RS_FILTER_BILINEAR, in_size, out_size, 0u, out_size, bounds, coefs, ksize);
 }
 
 // One image of the launch.  Table offsets count int32 words from the launch's table base.
@@ -134,6 +205,38 @@ inline bool resample_plan(ResampleJob &j, const int32_t *tab, uint32_t lds_cap =
     j.rb = rb;
     j.bands = (j.out_h + rb - 1u) / rb;
     return true;
+}
+
+// ---- runs of bands.  Under wide filters the source rows of neighbouring bands overlap, and every band passes the rows
+// it shares with its neighbour through the horizontal pass again.  A workgroup that takes a run of `bpr` consecutive bands keeps the
+// shared rows in LDS instead (RBand::roll_*).  Planner side: which plans may take the route, and what they would save. ----
+constexpr uint32_t RS_ROLL_DW = 8;  // dwords a lane carries through one slab of the move
+// Σ band source rows and the source rows the image reads; false where a band takes more than one chunk (those keep their bands)
+inline bool resample_band_rows(const ResampleJob &j, const int32_t *tab, uint64_t &passed, uint32_t &read) {
+    const int32_t *vb = tab + j.vb;
+    passed = 0;
+    for (uint32_t r0 = 0; r0 < j.out_h; r0 += j.rb) {
+        const uint32_t r1 = r0 + j.rb < j.out_h ? r0 + j.rb : j.out_h;
+        const uint32_t s0 = (uint32_t)vb[2 * r0], s1 = (uint32_t)(vb[2 * (r1 - 1u)] + vb[2 * (r1 - 1u) + 1]);
+        if (s1 - s0 > j.cap_rows) return false;
+        passed += s1 - s0;
+    }
+    read = (uint32_t)(vb[2 * (j.out_h - 1u)] + vb[2 * (j.out_h - 1u) + 1]) - (uint32_t)vb[0];
+    return true;
+}
+// bands per run for a job under `filter` (0: the job keeps its bands).  `knob`: 0 the rule below; 1 never; 2 / 4 / 8 that many for every
+// candidate (tools/filter_bench.py measures the routes against each other with it).  Candidates are BICUBIC and LANCZOS jobs of at
+// least two one-chunk bands.  The rule is the measurement's (profiles/filters/filter_bench.json): plans whose redundancy
+// (Σ band source rows / source rows read) exceeds 1.30 — 1.31 is the lowest that won by more than the band route's own spread, 1.21
+// the highest that lost — with 8 bands per run where that still leaves four runs, else 4 (8 of 14 bands: two workgroups per image, 1.05-1.26 x).
+constexpr uint32_t RS_ROLL_MIN_PERCENT = 130, RS_ROLL_LONG_BANDS = 32;
+inline uint32_t resample_roll_bpr(const ResampleJob &j, const int32_t *tab, uint32_t filter, uint32_t knob) {
+    if (knob == 1u || (filter != RS_FILTER_BICUBIC && filter != RS_FILTER_LANCZOS) || j.bands < 2u) return 0u;
+    uint64_t passed;
+    uint32_t read;
+    if (!resample_band_rows(j, tab, passed, read)) return 0u;
+    if (knob == 2u || knob == 4u || knob == 8u) return knob;
+    return passed * 100u > (uint64_t)read * RS_ROLL_MIN_PERCENT ? (j.bands >= RS_ROLL_LONG_BANDS ? 8u : 4u) : 0u;
 }
 
 #ifdef JPGPU_RS_DEVICE_BODY
@@ -183,7 +286,13 @@ struct RBand {
         rows_of(j, tab, band, r0, r1, s0, s1);
         const uint32_t c0 = s0 + chunk * j.cap_rows, c1 = min(c0 + j.cap_rows, s1);
         if (c0 >= c1 || x0 >= x1) return;
-        const uint32_t nc = j.nc, nx = x1 - x0, nrows = c1 - c0, units = ((nrows + RS_HROWS - 1u) / RS_HROWS) * nx;
+        hpass_rows(j, tab, c0, c1 - c0, 0u, x0, x1, tid, lds);
+    }
+    // its core: columns [x0, x1) of the `nrows` source rows from c0 into the LDS rows from l0; nrows > 0 and x0 < x1 (the runs of
+    // bands, DESIGN.md §4.15, pass only a band's new rows through it)
+    static __device__ __forceinline__ void hpass_rows(const ResampleJob &j, const JP_GLOBAL int32_t *tab, uint32_t c0, uint32_t nrows, uint32_t l0, uint32_t x0,
+                                                       uint32_t x1, uint32_t tid, uint8_t *lds) {
+        const uint32_t nc = j.nc, nx = x1 - x0, units = ((nrows + RS_HROWS - 1u) / RS_HROWS) * nx;
         const size_t src_pitch = (size_t)j.in_w * nc;
         const JP_GLOBAL int32_t *hb = tab + j.hb;
         const JP_GLOBAL int32_t *hk = tab + j.hk;
@@ -229,7 +338,7 @@ struct RBand {
 #pragma unroll
             for (uint32_t i = 0; i < RS_HROWS; i++) {
                 if (row0 + i >= nrows) continue;
-                uint8_t *o = lds + (row0 + i) * j.pitch + xx * nc;
+                uint8_t *o = lds + (l0 + row0 + i) * j.pitch + xx * nc;
 #pragma unroll
                 for (uint32_t c = 0; c < 4; c++)
                     if (c < nc) {
@@ -252,7 +361,12 @@ struct RBand {
         rows_of(j, tab, band, r0, r1, s0, s1);
         const uint32_t c0 = s0 + chunk * j.cap_rows, c1 = min(c0 + j.cap_rows, s1);
         if (c0 >= c1 || x0 >= x1) return;
-        const uint32_t nx = x1 - x0, nrows = c1 - c0, units = ((nrows + RS_HROWS - 1u) / RS_HROWS) * nx;
+        hpass_walk_rows<SNC>(j, tab, c0, c1 - c0, 0u, x0, x1, tid, lds);
+    }
+    template <uint32_t SNC>
+    static __device__ __forceinline__ void hpass_walk_rows(const ResampleJob &j, const JP_GLOBAL int32_t *tab, uint32_t c0, uint32_t nrows, uint32_t l0, uint32_t x0,
+                                                            uint32_t x1, uint32_t tid, uint8_t *lds) {
+        const uint32_t nx = x1 - x0, units = ((nrows + RS_HROWS - 1u) / RS_HROWS) * nx;
         const size_t src_pitch = (size_t)j.in_w * SNC;
         const JP_GLOBAL int32_t *hb = tab + j.hb;
         const JP_GLOBAL int32_t *hk = tab + j.hk;
@@ -297,7 +411,7 @@ struct RBand {
 #pragma unroll
             for (uint32_t i = 0; i < RS_HROWS; i++) {
                 if (row0 + i >= nrows) continue;
-                uint8_t *o = lds + (row0 + i) * j.pitch + xx * 3u;
+                uint8_t *o = lds + (l0 + row0 + i) * j.pitch + xx * 3u;
 #pragma unroll
                 for (uint32_t c = 0; c < SNC; c++) {
                     int32_t v = sum[i][c] >> RS_PRECISION_BITS;
@@ -321,7 +435,11 @@ struct RBand {
         rows_of(j, tab, band, r0, r1, s0, s1);
         const uint32_t c0 = s0 + chunk * j.cap_rows, c1 = min(c0 + j.cap_rows, s1);
         if (c0 >= c1 || x0 >= x1) return;
-        const uint32_t nx = x1 - x0, nrows = c1 - c0, units = ((nrows + RS_HROWS - 1u) / RS_HROWS) * nx;
+        hpass_cmyk_rows(j, tab, c0, c1 - c0, 0u, x0, x1, tid, lds);
+    }
+    static __device__ __forceinline__ void hpass_cmyk_rows(const ResampleJob &j, const JP_GLOBAL int32_t *tab, uint32_t c0, uint32_t nrows, uint32_t l0, uint32_t x0,
+                                                            uint32_t x1, uint32_t tid, uint8_t *lds) {
+        const uint32_t nx = x1 - x0, units = ((nrows + RS_HROWS - 1u) / RS_HROWS) * nx;
         const JP_GLOBAL int32_t *hb = tab + j.hb;
         const JP_GLOBAL int32_t *hk = tab + j.hk;
         const JP_GLOBAL uint32_t *src = (const JP_GLOBAL uint32_t *)j.src;
@@ -352,7 +470,7 @@ struct RBand {
 #pragma unroll
             for (uint32_t i = 0; i < RS_HROWS; i++) {
                 if (row0 + i >= nrows) continue;
-                uint8_t *o = lds + (row0 + i) * j.pitch + xx * 3u;
+                uint8_t *o = lds + (l0 + row0 + i) * j.pitch + xx * 3u;
 #pragma unroll
                 for (uint32_t c = 0; c < 3; c++) {
                     int32_t v = sum[i][c] >> RS_PRECISION_BITS;
@@ -369,6 +487,51 @@ struct RBand {
         if (KIND == 1u) hpass_walk<1u>(j, tab, band, chunk, x0, x1, tid, lds);
         else if (KIND == 4u) hpass_cmyk(j, tab, band, chunk, x0, x1, tid, lds);
         else hpass(j, tab, band, chunk, x0, x1, tid, lds);
+    }
+
+    template <uint32_t KIND>
+    static __device__ __forceinline__ void hpass_rows_of(const ResampleJob &j, const JP_GLOBAL int32_t *tab, uint32_t c0, uint32_t nrows, uint32_t l0, uint32_t tid,
+                                                         uint8_t *lds) {
+        if (KIND == 1u) hpass_walk_rows<1u>(j, tab, c0, nrows, l0, 0u, j.out_w, tid, lds);
+        else if (KIND == 4u) hpass_cmyk_rows(j, tab, c0, nrows, l0, 0u, j.out_w, tid, lds);
+        else hpass_rows(j, tab, c0, nrows, l0, 0u, j.out_w, tid, lds);
+    }
+
+    // ---- runs of bands: what band `band` (not the first of its run) keeps of the band before.  The rows [s0, p1) both read lie `shift`
+    // rows too high in LDS (`keep` of them); its new rows are [n0, s1).  (xmin and xmin + n never decrease from one output row to the next.)
+    static __device__ __forceinline__ void roll_of(const ResampleJob &j, const JP_GLOBAL int32_t *tab, uint32_t band, uint32_t &shift, uint32_t &keep, uint32_t &n0,
+                                                   uint32_t &s0, uint32_t &s1) {
+        uint32_t r0, r1, p0, p1;
+        rows_of(j, tab, band - 1u, r0, r1, p0, p1);
+        rows_of(j, tab, band, r0, r1, s0, s1);
+        shift = s0 - p0;
+        keep = p1 > s0 ? p1 - s0 : 0u;
+        n0 = max(p1, s0);
+    }
+    // The move of the kept rows down by `shift` rows, slab by slab of RS_NT * RS_ROLL_DW dwords.  It goes toward lower addresses and
+    // overlaps itself: a slab is READ into registers by every lane, then — behind a barrier — WRITTEN, and the next slab's reads wait
+    // for another barrier.  (A slab's destination lies below its own source, so it never reaches a later slab's source.)
+    static __device__ __forceinline__ uint32_t roll_slabs(const ResampleJob &j, uint32_t keep) {
+        return (keep * (j.pitch >> 2) + RS_NT * RS_ROLL_DW - 1u) / (RS_NT * RS_ROLL_DW);
+    }
+    static __device__ __forceinline__ void roll_read(const ResampleJob &j, uint32_t shift, uint32_t keep, uint32_t slab, uint32_t tid, const uint8_t *lds,
+                                                     uint32_t (&reg)[RS_ROLL_DW]) {
+        const uint32_t total = keep * (j.pitch >> 2), off = shift * (j.pitch >> 2);
+        const uint32_t *w = reinterpret_cast<const uint32_t *>(lds);
+#pragma unroll
+        for (uint32_t k = 0; k < RS_ROLL_DW; k++) {
+            const uint32_t d = (slab * RS_ROLL_DW + k) * RS_NT + tid;
+            reg[k] = d < total ? w[d + off] : 0u;
+        }
+    }
+    static __device__ __forceinline__ void roll_write(const ResampleJob &j, uint32_t keep, uint32_t slab, uint32_t tid, uint8_t *lds, const uint32_t (&reg)[RS_ROLL_DW]) {
+        const uint32_t total = keep * (j.pitch >> 2);
+        uint32_t *w = reinterpret_cast<uint32_t *>(lds);
+#pragma unroll
+        for (uint32_t k = 0; k < RS_ROLL_DW; k++) {
+            const uint32_t d = (slab * RS_ROLL_DW + k) * RS_NT + tid;
+            if (d < total) w[d] = reg[k];
+        }
     }
 
     // the share of source rows [c0, c1) (in LDS) in the four sums of destination dword q: where its bytes lie in one output row at a
@@ -466,5 +629,8 @@ namespace jpgpu {
 // (rgb: the instance whose horizontal pass converts jobs with src_nc != 0 — a batch created with JPGPU_BATCH_RGB_OUTPUT)
 hipError_t launch_resample_band(const ResampleJob *d_jobs, const int32_t *d_tab, uint32_t n_images, uint32_t max_bands, uint32_t lds_bytes, hipStream_t stream,
                                 bool rgb = false);
+// runs of bands: image i takes d_bpr[i] consecutive bands per workgroup (0: not in this launch); max_runs over the images
+hipError_t launch_resample_run(const ResampleJob *d_jobs, const int32_t *d_tab, const uint32_t *d_bpr, uint32_t n_images, uint32_t max_runs, uint32_t lds_bytes,
+                               hipStream_t stream);
 }  // namespace jpgpu
 #endif

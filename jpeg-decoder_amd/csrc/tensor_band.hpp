@@ -346,5 +346,8 @@ namespace jpgpu {
 // max_bands / lds_bytes (the rows') over the jobs; rgb: the instances whose horizontal pass converts jobs with src_nc != 0
 hipError_t launch_resample_tensor(const TensorJob *d_jobs, const int32_t *d_tab, const void *d_ttab, uint32_t elem_bytes, uint32_t n_images, uint32_t max_bands,
                                   uint32_t lds_bytes, hipStream_t stream, bool rgb = false);
+// runs of bands (resample_band.hpp): image i takes d_bpr[i] consecutive bands per workgroup (0: not in this launch)
+hipError_t launch_resample_tensor_run(const TensorJob *d_jobs, const int32_t *d_tab, const void *d_ttab, const uint32_t *d_bpr, uint32_t elem_bytes, uint32_t n_images,
+                                      uint32_t max_runs, uint32_t lds_bytes, hipStream_t stream);
 }  // namespace jpgpu
 #endif

@@ -9,7 +9,7 @@ import ctypes as C
 import numpy as np
 
 from . import _native as N
-from .batch import flip_bytes, output_size_pair, window_structs
+from .batch import filter_id, flip_bytes, output_size_pair, window_structs
 from .decoder import CODING_PROCESSES, PIXEL_FORMATS, ImageInfo
 from .error import check, error_for_status
 from .worker import color_transform_id
@@ -76,7 +76,7 @@ class Pipeline:
 
     def decode(self, streams, download=True, dense=False, device_entropy=True, scale=None, color_transform=None, max_decoding_buffer_size=None,
                gather=False, host_light=None, input_pinned=False, progressive_on_host=False, windows=None, output_size=None,
-               tensor=None, flips=None, rgb=False, fit=None):
+               tensor=None, flips=None, rgb=False, fit=None, filter=None):
         """-> list with, per stream, a numpy uint8 array of the decoded pixels (``Decoder.decode()``'s Vec<u8>) or the
         ``Error`` instance that stream produced.  download=False leaves the pixels in HBM (see ``device_pointer``); dense=True sends all
         64 coefficients of every block over PCIe instead of the compact form (same pixels, A/B switch); device_entropy=True
@@ -112,7 +112,11 @@ class Pipeline:
         every stream's source — its window, else its output after `scale` — is resampled to a size of its own and laid into the output
         size, cropped and filled: ``Fit("shorter_side_crop", size=256)`` with output_size=(224, 224) is the evaluation
         transform ``Resize(256)`` + ``CenterCrop(224)``, ``Fit("letterbox", fill=(114, 114, 114))`` the aspect-preserving fit with constant
-        padding.  ``placement(i)`` gives the stream's (rw, rh, x, y); a stream whose rule is refused (a side above 65535) fails alone."""
+        padding.  ``placement(i)`` gives the stream's (rw, rh, x, y); a stream whose rule is refused (a side above 65535) fails alone.
+        filter: None or "bilinear" (the default), "box", "hamming", "bicubic", "lanczos", or a JPGPU_FILTER_* id (jpgpu_pipeline_set_filter,
+        set on every call; any other than bilinear needs output_size, else FormatError and nothing is decoded; an id the library does not
+        know: FormatError): every resample is Pillow's ``Image.resize(size, F)`` with that filter — CLIP's transform is
+        ``fit=Fit("shorter_side_crop", size=224), output_size=(224, 224), filter="bicubic"``."""
         if isinstance(streams, PinnedFiles):
             bufs = None
             n = len(streams)
@@ -124,6 +128,7 @@ class Pipeline:
         wins = window_structs(windows, n)  # (raises on a list of the wrong length, before anything native is called)
         size = (0, 0) if output_size is None else output_size_pair(output_size)
         flip_arr = flip_bytes(flips, n)
+        filt = filter_id(filter)
         fmt = None if tensor is None else tensor.struct()
         self._shape = None if tensor is None else (tensor.numpy_dtype, size[1], size[0])
         L = N.lib()
@@ -135,6 +140,8 @@ class Pipeline:
         st = L.jpgpu_pipeline_set_tensor_output(self._h, None if fmt is None else C.byref(fmt))
         check(st, L.jpgpu_pipeline_last_error(self._h) if st else b"")
         check(L.jpgpu_pipeline_set_rgb_output(self._h, 1 if rgb else 0), b"set_rgb_output")
+        st = L.jpgpu_pipeline_set_filter(self._h, filt)
+        check(st, L.jpgpu_pipeline_last_error(self._h) if st else b"")
         fit_s = None if fit is None else fit.struct()
         st = L.jpgpu_pipeline_set_fit(self._h, None if fit_s is None else C.byref(fit_s))
         check(st, L.jpgpu_pipeline_last_error(self._h) if st else b"")
