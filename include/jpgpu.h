@@ -326,6 +326,57 @@ typedef struct jpgpu_fit {
     uint32_t reserved; /* 0 */
 } jpgpu_fit;
 int jpgpu_fit_placement(const jpgpu_fit *fit, uint32_t src_w, uint32_t src_h, uint32_t out_w, uint32_t out_h, jpgpu_placement *out);
+/* ---- Affine warps behind the fixed output size: rotate, shear, translate per image --------------------------------
+ * jpgpu_batch_create_placed with a warp stage behind the resample.  With R the image's u8 result of out_w x out_h, exactly as the same
+ * batch without a warp defines it (placement fill included), and F the image's flip (tensor batches only):
+ *     out(Y, X, c)  = Warp_i( F ? mirror_columns(R) : R )(Y, X, c)        u8 batches: these bytes, interleaved
+ *     elem(c, Y, X) = T[c][ out(Y, X, c) ]                                 tensor batches, CHW
+ * The flip comes BEFORE the warp (torchvision's order: flip, then the policy).  Warp is Pillow's
+ * Image.transform((out_w, out_h), Image.AFFINE, m, resample, fillcolor=fill) of the source S = R (W x H = out_w x out_h): m[0..5] is the
+ * inverse map, output pixel -> source position; the output starts as `fill` — the warp's own, separate from a placement's — and a tensor
+ * element outside the source is T[c][fill[c]].
+ *   N  — JPGPU_WARP_NEAREST, m[1] != 0 || m[3] != 0: 16.16 fixed point.  FIX(v) = (int)floor(v * 65536.0 + 0.5); a0, a1, a3, a4 = FIX of
+ *        m[0], m[1], m[3], m[4]; a2 = FIX(m[2] + m[0]*0.5 + m[1]*0.5), a5 = FIX(m[5] + m[3]*0.5 + m[4]*0.5) (doubles, one operation per
+ *        statement, left to right); xi = (a2 + X a0 + Y a1) >> 16, yi = (a5 + X a3 + Y a4) >> 16 (arithmetic shifts);
+ *        0 <= xi < W && 0 <= yi < H: out = S[yi][xi], else the fill stays.
+ *   N-sep — JPGPU_WARP_NEAREST, m[1] == 0 && m[3] == 0: an index per axis, a sequential sum of doubles (jpgpu_warp_nearest_axis):
+ *        xo = m[2] + m[0]*0.5; for X = 0 .. out_w - 1: xs[X] = xo < 0.0 ? -1 : (int)xo, then xo += m[0]; ys likewise from m[5], m[4];
+ *        out = S[ys[Y]][xs[X]] where both indices are in range.  (Other pixels than rule N gives, as in Pillow.)
+ *   B  — JPGPU_WARP_BILINEAR, any matrix: IEEE double, no fused multiply-add.  xin = X + 0.5, yin = Y + 0.5;
+ *        xo = (m0 xin + m1 yin) + m2, yo likewise; xo < 0 || xo >= W || yo < 0 || yo >= H: the fill stays; else xo -= 0.5, yo -= 0.5,
+ *        x = floor(xo), y = floor(yo), dx = xo - x, dy = yo - y; x0 = clamp(x, 0, W-1), x1 = clamp(x+1, 0, W-1), r0 = clamp(y, 0, H-1);
+ *        per channel v1 = p[r0][x0] + (p[r0][x1] - p[r0][x0]) dx; v2 the same on row y+1 if 0 <= y+1 < H, else v1;
+ *        v = v1 + (v2 - v1) dy; out = (uint8)v, truncated.
+ * A matrix is refused (jpgpu_warp_check: JPGPU_ERR_FORMAT) when a coefficient is not finite, |m[0]|, |m[1]|, |m[3]| or |m[4]| is above
+ * 16000, or at a corner (X, Y) of (0,0), (out_w,0), (0,out_h), (out_w,out_h) |X m0 + Y m1 + m2| or |X m3 + Y m4 + m5| is above 32000:
+ * inside these bounds every sum of rule N fits 32 bits.
+ * `warp` NULL IS jpgpu_batch_create_placed: same kernels, bytes and path.  Otherwise every image starts with the identity; the batch's
+ * resample launch is the u8 one of the same arguments and writes an arena the batch owns, one more launch behind it warps into the
+ * output arena.  jpgpu_batch_path is the u8 batch's path, then "+warp" or "+warp:bilinear", then "+tensor" with a format.  A warp needs
+ * an output size (JPGPU_ERR_FORMAT); planar ColorTransform None images stay JPGPU_ERR_UNSUPPORTED; an unknown filter or reserved != 0
+ * is JPGPU_ERR_FORMAT. */
+enum { JPGPU_WARP_NEAREST = 0, JPGPU_WARP_BILINEAR = 1 };
+typedef struct jpgpu_warp {
+    double m[6];
+} jpgpu_warp;
+typedef struct jpgpu_warp_options {
+    uint32_t filter; /* JPGPU_WARP_NEAREST 0, JPGPU_WARP_BILINEAR 1 */
+    uint8_t fill[4];
+    uint32_t reserved; /* 0 */
+} jpgpu_warp_options;
+int jpgpu_batch_create_warped(int device, const jpgpu_image_desc *descs, const jpgpu_window *windows, const jpgpu_placement *placements,
+                              const uint8_t *fill, uint16_t out_w, uint16_t out_h, const jpgpu_tensor_format *format, const jpgpu_warp_options *warp,
+                              uint32_t n_images, uint32_t flags, jpgpu_batch **out);
+/* The matrix of every image (`warps`: n_images entries; NULL: identities) from the next jpgpu_batch_decode enqueued on: fields of the
+ * images' job records, sent with them on the decode's stream (a decode already enqueued keeps its matrices: "Batch calls on caller
+ * streams" below).  One refused matrix refuses the call (JPGPU_ERR_FORMAT) and nothing is changed.  JPGPU_ERR_UNSUPPORTED on a batch
+ * without a warp. */
+int jpgpu_batch_set_warps(jpgpu_batch *b, const jpgpu_warp *warps);
+/* Pure host functions (no device needed): the refusal rule above for an output of out_w x out_h (JPGPU_OK / JPGPU_ERR_FORMAT), and the
+ * N-sep index table of one axis — idx[X] for X < out_size from the scale a (m[0] / m[4]) and the offset b (m[2] / m[5]); a position no
+ * int holds gives INT32_MAX, one that is no number -1. */
+int jpgpu_warp_check(const jpgpu_warp *warp, uint32_t out_w, uint32_t out_h);
+int jpgpu_warp_nearest_axis(double a, double b, uint32_t out_size, int32_t *idx);
 void jpgpu_batch_destroy(jpgpu_batch *b);
 const char *jpgpu_batch_last_error(const jpgpu_batch *b);
 
@@ -404,7 +455,7 @@ int jpgpu_batch_upload_compact(jpgpu_batch *b, uint32_t image, uint32_t comp, co
  * of it there: it affects only decodes enqueued LATER, the one already enqueued runs with the tables, classes, coefficients, arenas
  * and flips the batch held when it was enqueued.  This covers jpgpu_batch_set_quantization_table ("the next decode" below means the
  * next one enqueued), jpgpu_batch_set_range_hint, jpgpu_batch_set_range_class, jpgpu_batch_upload, jpgpu_batch_upload_compact,
- * jpgpu_batch_bind, jpgpu_batch_set_flips, jpgpu_batch_scan_ranges, jpgpu_batch_classify_on_device, and the decode that follows any
+ * jpgpu_batch_bind, jpgpu_batch_set_flips, jpgpu_batch_set_warps, jpgpu_batch_scan_ranges, jpgpu_batch_classify_on_device, and the decode that follows any
  * of them.  The library orders its own copies: where a table can only be rewritten by a blocking copy, the call that rewrites it
  * (jpgpu_batch_upload; the next decode, scan or classification after the others) first waits on the host for the work the batch
  * has enqueued — only when something did change, so a decode behind a decode gains no synchronisation.

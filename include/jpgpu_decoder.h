@@ -265,6 +265,13 @@ int jpgpu_pipeline_set_filter(jpgpu_pipeline *p, uint32_t filter);
  * kept sub-batches anew; fresh windows at the same fit are re-placed in place with them.  Composes with the scale, the tensor format,
  * flips, RGB output and windows.  An unknown mode, reserved != 0 or size 0 with mode 1: JPGPU_ERR_FORMAT, nothing changes. */
 int jpgpu_pipeline_set_fit(jpgpu_pipeline *p, const jpgpu_fit *fit);
+/* A warp stage behind the output size for every image of the calls that follow (sticky; NULL: off — the routes, launches and bytes
+ * without it): the sub-batches are created with jpgpu_batch_create_warped (jpgpu.h: Pillow's Image.transform(size, AFFINE, m, NEAREST or
+ * BILINEAR, fillcolor=warp->fill) of every image's u8 result, a flip first); the matrices come per call with
+ * jpgpu_pipeline_decode_warped.  A warp needs an output size: without one the next decode fails whole with JPGPU_ERR_FORMAT before
+ * anything is decoded.  Changed options create the kept sub-batches anew.  Composes with the scale, windows, the filter, a fit, RGB
+ * output, the tensor format and flips.  An unknown filter or reserved != 0: JPGPU_ERR_FORMAT, nothing changes. */
+int jpgpu_pipeline_set_warp(jpgpu_pipeline *p, const jpgpu_warp_options *warp);
 /* The placement image `image` of the last call was decoded with: jpgpu_fit_placement of its source size, (out_w, out_h, 0, 0) without a
  * fit.  JPGPU_ERR_FORMAT without an output size, for an image without a frame, or one whose window or rule was refused. */
 int jpgpu_pipeline_image_placement(const jpgpu_pipeline *p, uint32_t image, jpgpu_placement *out);
@@ -300,6 +307,13 @@ int jpgpu_pipeline_decode_windowed(jpgpu_pipeline *p, const uint8_t *const *data
  * are set in place (jpgpu_batch_set_flips), the windows as jpgpu_pipeline_decode_windowed sets them. */
 int jpgpu_pipeline_decode_augmented(jpgpu_pipeline *p, const uint8_t *const *data, const size_t *len, const jpgpu_window *windows,
                                     const uint8_t *flips, uint32_t n_images, uint32_t flags);
+/* jpgpu_pipeline_decode_augmented with a matrix per image (`warps`: n_images entries; NULL with jpgpu_pipeline_set_warp in force:
+ * identities; NULL without: exactly jpgpu_pipeline_decode_augmented).  `warps` without warp options fails the call with JPGPU_ERR_FORMAT
+ * before anything is decoded.  A matrix jpgpu_warp_check refuses for the output size gives THAT image JPGPU_ERR_FORMAT; every other
+ * image of the call is decoded.  Fresh matrices never create a kept sub-batch anew: they are set in place (jpgpu_batch_set_warps), like
+ * the flips. */
+int jpgpu_pipeline_decode_warped(jpgpu_pipeline *p, const uint8_t *const *data, const size_t *len, const jpgpu_window *windows,
+                                 const uint8_t *flips, const jpgpu_warp *warps, uint32_t n_images, uint32_t flags);
 /* The window image i of the last call was decoded with: what the caller passed, or 0, 0, W, H of the output grid when it had none
  * (JPGPU_ERR_FORMAT for an image without a frame or whose window was refused). */
 int jpgpu_pipeline_image_window(const jpgpu_pipeline *p, uint32_t image, jpgpu_window *out);

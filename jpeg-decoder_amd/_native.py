@@ -91,6 +91,17 @@ class Placement(C.Structure):
 
 
 FIT_STRETCH, FIT_SHORTER_SIDE_CROP, FIT_LETTERBOX = 0, 1, 2
+WARP_NEAREST, WARP_BILINEAR = 0, 1
+
+
+class Warp(C.Structure):
+    """jpgpu_warp: Pillow's six AFFINE coefficients (the inverse map: output pixel -> source position)."""
+    _fields_ = [("m", C.c_double * 6)]
+
+
+class WarpOptionsStruct(C.Structure):
+    """jpgpu_warp_options: filter (WARP_*), fill[4], reserved = 0."""
+    _fields_ = [("filter", C.c_uint32), ("fill", C.c_uint8 * 4), ("reserved", C.c_uint32)]
 
 
 class FitStruct(C.Structure):
@@ -160,6 +171,11 @@ _PROTOS = {
     "jpgpu_resample_coefficients_range": (C.c_int, [C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.POINTER(C.c_uint32)]),
     "jpgpu_fit_placement": (C.c_int, [C.POINTER(FitStruct), C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(Placement)]),
     "jpgpu_batch_set_flips": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "jpgpu_batch_create_warped": (C.c_int, [C.c_int, C.POINTER(ImageDesc), C.POINTER(Window), C.POINTER(Placement), C.c_void_p, C.c_uint16, C.c_uint16,
+                                            C.POINTER(TensorFormatStruct), C.POINTER(WarpOptionsStruct), C.c_uint32, C.c_uint32, C.POINTER(C.c_void_p)]),
+    "jpgpu_batch_set_warps": (C.c_int, [C.c_void_p, C.POINTER(Warp)]),
+    "jpgpu_warp_check": (C.c_int, [C.POINTER(Warp), C.c_uint32, C.c_uint32]),
+    "jpgpu_warp_nearest_axis": (C.c_int, [C.c_double, C.c_double, C.c_uint32, C.c_void_p]),
     "jpgpu_tensor_table": (C.c_int, [C.POINTER(TensorFormatStruct), C.c_uint32, C.c_void_p]),
     "jpgpu_resample_coefficients_filtered": (C.c_int, [C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.POINTER(C.c_uint32)]),
     "jpgpu_resample_coefficients_range_filtered": (C.c_int, [C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.POINTER(C.c_uint32)]),
@@ -222,6 +238,9 @@ _PROTOS = {
     "jpgpu_pipeline_decode": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), C.c_uint32, C.c_uint32]),
     "jpgpu_pipeline_decode_windowed": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), C.POINTER(Window), C.c_uint32, C.c_uint32]),
     "jpgpu_pipeline_decode_augmented": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), C.POINTER(Window), C.c_void_p, C.c_uint32, C.c_uint32]),
+    "jpgpu_pipeline_decode_warped": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), C.POINTER(Window), C.c_void_p, C.POINTER(Warp), C.c_uint32,
+                                               C.c_uint32]),
+    "jpgpu_pipeline_set_warp": (C.c_int, [C.c_void_p, C.POINTER(WarpOptionsStruct)]),
     "jpgpu_pipeline_image_window": (C.c_int, [C.c_void_p, C.c_uint32, C.POINTER(Window)]),
     "jpgpu_pipeline_image_status": (C.c_int, [C.c_void_p, C.c_uint32]),
     "jpgpu_pipeline_image_error": (C.c_char_p, [C.c_void_p, C.c_uint32]),

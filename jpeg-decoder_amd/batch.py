@@ -1,5 +1,6 @@
 """Batch driver mirror (include/jpgpu.h jpgpu_batch_*): N independent images per launch."""
 import ctypes as C
+import math
 
 import numpy as np
 
@@ -180,6 +181,79 @@ def placement_structs(placements, n):
     return arr
 
 
+class WarpOptions:
+    """The warp stage of a batch or a pipeline (jpgpu_warp_options): ``filter`` "nearest" or "bilinear" — Pillow's
+    ``Image.transform(size, Image.AFFINE, m, Image.NEAREST / Image.BILINEAR, fillcolor=fill)`` — and ``fill``, up to four bytes in the
+    output's channel order: the warp's own fill, separate from a placement's."""
+    FILTERS = {"nearest": N.WARP_NEAREST, "bilinear": N.WARP_BILINEAR}
+
+    def __init__(self, filter="nearest", fill=(0, 0, 0, 0)):
+        name = str(filter).lower()
+        if name not in self.FILTERS:
+            raise ValueError(f"warp filter {filter!r}: one of {sorted(self.FILTERS)}")
+        self.filter, self.fill = name, fill_tuple(fill)
+
+    def struct(self):
+        s = N.WarpOptionsStruct()
+        s.filter, s.reserved = self.FILTERS[self.filter], 0
+        for c in range(4):
+            s.fill[c] = self.fill[c]
+        return s
+
+    def __eq__(self, other):
+        return isinstance(other, WarpOptions) and (self.filter, self.fill) == (other.filter, other.fill)
+
+    def __repr__(self):
+        return f"WarpOptions({self.filter!r}, fill={self.fill})"
+
+
+def warp_structs(warps, n):
+    """`warps`: None or a list with six coefficients or None (the identity) per image -> (ctypes array of jpgpu_warp or None)."""
+    if warps is None:
+        return None
+    warps = list(warps)
+    if len(warps) != n:
+        raise ValueError(f"{len(warps)} warps for {n} images")
+    arr = (N.Warp * max(n, 1))()
+    for i, m in enumerate(warps):
+        m = (1.0, 0.0, 0.0, 0.0, 1.0, 0.0) if m is None else tuple(float(v) for v in m)
+        if len(m) != 6:
+            raise ValueError(f"warp {m!r} of image {i}: six coefficients")
+        arr[i].m[:] = m
+    return arr
+
+
+def warp_check(m, output_size):
+    """jpgpu_warp_check: True when the six coefficients are accepted for ``output_size`` = (w, h) (finite, |m0|, |m1|, |m3|,
+    |m4| <= 16000, every corner of the output within +-32000 of the source's origin)."""
+    arr = warp_structs([m], 1)
+    return N.lib().jpgpu_warp_check(arr, int(output_size[0]), int(output_size[1])) == N.OK
+
+
+def warp_nearest_axis(a, b, out_size):
+    """jpgpu_warp_nearest_axis: the index table of one axis of a NEAREST warp without rotation or shear (scale a, offset b) as the batch
+    computes it (pure host function) -> int32 (out_size,)."""
+    idx = np.zeros(max(int(out_size), 1), np.int32)
+    check(N.lib().jpgpu_warp_nearest_axis(float(a), float(b), int(out_size), idx.ctypes.data), b"jpgpu_warp_nearest_axis: refused")
+    return idx[: int(out_size)]
+
+
+def rotate_matrix(angle, size, center=None, translate=None):
+    """The six coefficients ``Image.rotate(angle, center=, translate=)`` builds without ``expand`` for an image of ``size`` = (w, h):
+    counter-clockwise by ``angle`` degrees about ``center`` (default (w / 2, h / 2)), then moved by ``translate``."""
+    w, h = size
+    angle = angle % 360.0
+    cx, cy = (w / 2.0, h / 2.0) if center is None else (center[0], center[1])
+    tx, ty = (0, 0) if translate is None else (translate[0], translate[1])
+    r = -math.radians(angle)
+    m = [round(math.cos(r), 15), round(math.sin(r), 15), 0.0, round(-math.sin(r), 15), round(math.cos(r), 15), 0.0]
+    x, y = -cx - tx, -cy - ty
+    m[2], m[5] = m[0] * x + m[1] * y + m[2], m[3] * x + m[4] * y + m[5]
+    m[2] += cx
+    m[5] += cy
+    return tuple(m)
+
+
 def flip_bytes(flips, n):
     """`flips`: None or one truth value per image -> (ctypes array of n bytes or None)."""
     if flips is None:
@@ -226,10 +300,16 @@ class Batch:
 
     filter: None or "bilinear" (the default: nothing changes), "box", "hamming", "bicubic", "lanczos", or a JPGPU_FILTER_* id
     (JPGPU_BATCH_FILTER in the flags; needs an output_size, else UnsupportedError): every resample of the batch is Pillow's
-    ``Image.resize(size, F)`` with that filter; `path` names it behind "+resize", as in "+resize:bicubic"."""
+    ``Image.resize(size, F)`` with that filter; `path` names it behind "+resize", as in "+resize:bicubic".
+
+    warp: None or a WarpOptions (jpgpu_batch_create_warped; needs an output_size, else FormatError).  Every image's result of the above —
+    its u8 pixels of the output size, placement fill included, mirrored first when the image is flipped — is then read through six
+    coefficients per image, ``Image.transform((w, h), Image.AFFINE, m, NEAREST or BILINEAR, fillcolor=warp.fill)``, and written as bytes
+    or, with `tensor`, through the table.  Every image starts with the identity; ``set_warps([...])`` sets the
+    matrices from the next decode on.  `path` gains "+warp" or "+warp:bilinear" before "+tensor"."""
 
     def __init__(self, descs, device=0, flags=N.BATCH_DEFAULT, windows=None, output_size=None, tensor=None, rgb=False, placements=None, fill=None,
-                 filter=None):
+                 filter=None, warp=None):
         self._h = C.c_void_p()
         arr = (N.ImageDesc * len(descs))(*descs)
         wins = window_structs(windows, len(descs))
@@ -243,7 +323,14 @@ class Batch:
         self.filter = N.FILTER_NAMES[(flags >> 8) & 15] if (flags >> 8) & 15 < len(N.FILTER_NAMES) else (flags >> 8) & 15
         pls = placement_structs(placements, len(descs))
         self.fill = fill_tuple(fill)
-        if pls is not None:
+        self.warp = warp
+        if warp is not None:
+            w, h = self.output_size if self.output_size is not None else (0, 0)
+            fmt = tensor.struct() if tensor is not None else None
+            wo = warp.struct()
+            st = N.lib().jpgpu_batch_create_warped(device, arr, wins, pls, (C.c_uint8 * 4)(*self.fill), w, h, C.byref(fmt) if fmt is not None else None,
+                                                   C.byref(wo), len(descs), flags, C.byref(self._h))
+        elif pls is not None:
             w, h = self.output_size if self.output_size is not None else (0, 0)
             fmt = tensor.struct() if tensor is not None else None
             st = N.lib().jpgpu_batch_create_placed(device, arr, wins, pls, (C.c_uint8 * 4)(*self.fill), w, h, C.byref(fmt) if fmt is not None else None,
@@ -367,6 +454,12 @@ class Batch:
         without `tensor` raises UnsupportedError."""
         arr = flip_bytes(flips, self.n_images)
         self._check(N.lib().jpgpu_batch_set_flips(self._h, arr))
+
+    def set_warps(self, warps):
+        """jpgpu_batch_set_warps: six coefficients (or None: the identity) per image, None for identities throughout; in force from the
+        next decode on.  One refused matrix raises FormatError and changes nothing; a batch without `warp` raises UnsupportedError."""
+        arr = warp_structs(warps, self.n_images)
+        self._check(N.lib().jpgpu_batch_set_warps(self._h, arr))
 
     def download(self, image):
         n = self.out_bytes(image)

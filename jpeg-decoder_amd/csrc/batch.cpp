@@ -89,8 +89,8 @@ static int batch_resample_tables(jpgpu_batch *b) {
         b->rs_lds_bytes = std::max(b->rs_lds_bytes, j.lds_bytes);
     }
     const size_t roll_at = b->path.find("+roll");  // (the path names the route where any image took it; other windows may change that)
-    if (roll_at != std::string::npos) b->path.erase(roll_at);
-    if (b->rs_max_runs) b->path += "+roll";
+    if (roll_at != std::string::npos) b->path.erase(roll_at, 5);
+    if (b->rs_max_runs) b->path.insert(std::min(b->path.find("+warp"), b->path.size()), "+roll");  // (the last word of the u8 batch's path: in front of a warp's)
     B_HIP(batch_wait_enqueued(b));  // (a decode still queued reads the tables)
     if (b->rs_tab.size() > b->rs_tab_cap) {
         B_HIP(hipDeviceSynchronize());
@@ -150,12 +150,45 @@ static int batch_upload_tensor_jobs(jpgpu_batch *b, hipStream_t stream) {
     return JPGPU_OK;
 }
 
+// The WarpJobs of a warped batch and the N-sep tables behind them: every image's matrix, its flip, where it reads and writes.  From a
+// pinned mirror on the decode's stream, as the TensorJobs: a decode queued earlier keeps the matrices it was enqueued with.
+static size_t warp_jobs_bytes(const jpgpu_batch *b) { return b->descs.size() * (sizeof(WarpJob) + ((size_t)b->rs_w + b->rs_h) * sizeof(int32_t)); }
+static int batch_upload_warp_jobs(jpgpu_batch *b, hipStream_t stream) {
+    const uint32_t n = (uint32_t)b->descs.size();
+    if (!b->h_wp_jobs) {
+        B_HIP(hipHostMalloc((void **)&b->h_wp_jobs, warp_jobs_bytes(b), hipHostMallocDefault));
+        B_HIP(hipEventCreateWithFlags(&b->wp_sent, hipEventDisableTiming));
+    } else {
+        B_HIP(hipEventSynchronize(b->wp_sent));  // (the copy before this one has read the mirror)
+    }
+    WarpJob *jobs = reinterpret_cast<WarpJob *>(b->h_wp_jobs);
+    int32_t *tabs = reinterpret_cast<int32_t *>(b->h_wp_jobs + (size_t)n * sizeof(WarpJob));
+    const bool rgb = (b->flags & JPGPU_BATCH_RGB_OUTPUT) != 0;
+    for (uint32_t i = 0; i < n; i++) {
+        WarpJob &j = jobs[i];
+        j.src = b->d_wsrc + b->wsrc_off[i], j.dst = b->d_out + b->out_off[i];
+        j.w = b->rs_w, j.h = b->rs_h, j.nc = rgb ? 3u : b->descs[i].ncomp;
+        j.flip = (b->tn_es && b->tn_flips[i]) ? 1u : 0u;
+        j.fill = b->wp_fill, j.plane = b->rs_w * b->rs_h;
+        j.tab = i * (b->rs_w + b->rs_h);
+        warp_job_matrix(j, b->wp_m[i].m, b->wp_filter, tabs + j.tab);
+    }
+    B_HIP(hipMemcpyAsync(b->d_wp_jobs, b->h_wp_jobs, warp_jobs_bytes(b), hipMemcpyHostToDevice, stream));
+    B_HIP(hipEventRecord(b->wp_sent, stream));
+    b->wp_dirty = false;
+    return JPGPU_OK;
+}
+
 static int batch_refresh_jobs(jpgpu_batch *b, hipStream_t stream = nullptr) {
     // host-side classes are part of the launch tables (one launch per class: fused_bind); with device-side classes they
     // travel in a small table of their own, asynchronously, and the launch tables stay as they are
     const bool need_bind = b->jobs_dirty || (b->cls_dirty && !b->dev_classes);
     if (!need_bind && b->tn_dirty && b->d_coef && b->d_out) {  // (other flips alone: the TensorJobs, nothing else)
         int rc = batch_upload_tensor_jobs(b, stream);
+        if (rc) return rc;
+    }
+    if (!need_bind && b->wp_dirty && b->d_coef && b->d_out) {  // (other matrices or flips alone: the WarpJobs, nothing else)
+        int rc = batch_upload_warp_jobs(b, stream);
         if (rc) return rc;
     }
     if (!need_bind && !b->cls_dirty) return JPGPU_OK;
@@ -214,8 +247,12 @@ static int batch_refresh_jobs(jpgpu_batch *b, hipStream_t stream = nullptr) {
         if (rc) return rc;
     }
     if (b->rs_w) {
-        for (uint32_t i = 0; i < n; i++) b->rs_jobs[i].src = pix + pix_off[i], b->rs_jobs[i].dst = b->d_out + b->out_off[i];
-        if (b->tn_es) {
+        for (uint32_t i = 0; i < n; i++) b->rs_jobs[i].src = pix + pix_off[i], b->rs_jobs[i].dst = b->warp ? b->d_wsrc + b->wsrc_off[i] : b->d_out + b->out_off[i];
+        if (b->warp) {  // (the u8 resample of the same arguments writes the warp's source; the warp writes the output)
+            rc = batch_upload_warp_jobs(b, stream);
+            if (rc) return rc;
+        }
+        if (b->tn_es && !b->warp) {
             rc = batch_upload_tensor_jobs(b, stream);
             if (rc) return rc;
         } else if (b->placed) {
@@ -247,7 +284,7 @@ extern "C" {
 // placements, fill: those of jpgpu_batch_create_placed (NULL: none)
 static int batch_create(int device, const jpgpu_image_desc *descs, const jpgpu_window *windows, uint32_t rs_w, uint32_t rs_h,
                         const jpgpu_tensor_format *tensor, uint32_t n_images, uint32_t flags, jpgpu_batch **out,
-                        const jpgpu_placement *placements = nullptr, const uint8_t *fill = nullptr) {
+                        const jpgpu_placement *placements = nullptr, const uint8_t *fill = nullptr, const jpgpu_warp_options *warp = nullptr) {
     if (!out) return JPGPU_ERR_FORMAT;
     *out = nullptr;
     if (!descs || n_images == 0 || n_images > 65535) return JPGPU_ERR_FORMAT;
@@ -267,6 +304,14 @@ static int batch_create(int device, const jpgpu_image_desc *descs, const jpgpu_w
     const bool rgb = (flags & JPGPU_BATCH_RGB_OUTPUT) != 0;  // (every image gives three channels: the resample converts gray and CMYK)
     if (rgb && !resized)
         return set_err(b->err, JPGPU_ERR_UNSUPPORTED, "JPGPU_BATCH_RGB_OUTPUT needs an output size (jpgpu_batch_create_resized / _create_tensor)");
+    if (warp) {  // (every image starts with the identity)
+        if (!resized) return set_err(b->err, JPGPU_ERR_FORMAT, "a warp needs an output size");
+        if (warp->filter > WP_BILINEAR || warp->reserved != 0)
+            return set_err(b->err, JPGPU_ERR_FORMAT, "warp options: filter %u, reserved %u (JPGPU_WARP_NEAREST or JPGPU_WARP_BILINEAR, reserved 0)", warp->filter, warp->reserved);
+        b->warp = true, b->wp_filter = warp->filter;
+        b->wp_fill = (uint32_t)warp->fill[0] | ((uint32_t)warp->fill[1] << 8) | ((uint32_t)warp->fill[2] << 16) | ((uint32_t)warp->fill[3] << 24);
+        b->wp_m.assign(n_images, jpgpu_warp{{1.0, 0.0, 0.0, 0.0, 1.0, 0.0}});
+    }
     if (tensor) {  // (the format against the channels of every image of the call, before anything is allocated)
         if (!resized) return set_err(b->err, JPGPU_ERR_FORMAT, "a tensor format needs an output size");
         uint32_t nc_max = rgb ? 3u : 1u;
@@ -371,6 +416,12 @@ static int batch_create(int device, const jpgpu_image_desc *descs, const jpgpu_w
         for (uint32_t i = 0; i < n_images; i++) lens[i] = (size_t)rs_w * rs_h * (rgb ? 3u : b->descs[i].ncomp) * (tensor ? b->tn_es : 1u);
         b->out_bytes = arena_layout(lens, b->out_off, b->out_len);
     }
+    std::vector<size_t> wsrc_len;
+    size_t wsrc_bytes = 0;
+    if (b->warp) {  // (what the u8 batch's output arena would be)
+        for (uint32_t i = 0; i < n_images; i++) lens[i] = (size_t)rs_w * rs_h * (rgb ? 3u : b->descs[i].ncomp);
+        wsrc_bytes = arena_layout(lens, b->wsrc_off, wsrc_len);
+    }
 
     {
         std::vector<uint32_t> keys;
@@ -400,6 +451,7 @@ static int batch_create(int device, const jpgpu_image_desc *descs, const jpgpu_w
     if (b->placed) b->path += "+place";
     if (resized) b->path += "+resize";
     if (filter) b->path += std::string(":") + resample_filter_name(filter);
+    if (b->warp) b->path += b->wp_filter == WP_BILINEAR ? "+warp:bilinear" : "+warp";
     if (tensor) b->path += "+tensor";
     const size_t full = arena_layout(b->out_full_len);  // (what the whole images take)
     if (!(flags & JPGPU_BATCH_EXTERNAL_BUFFERS)) {
@@ -413,15 +465,24 @@ static int batch_create(int device, const jpgpu_image_desc *descs, const jpgpu_w
     if (resized) {  // (the same headroom for other windows, in the intermediate arena)
         b->pix_cap = b->win.empty() ? b->pix_bytes : arena_headroom(b->pix_bytes, full);
         B_HIP(hipMalloc((void **)&b->d_pix, b->pix_cap));
+        if (b->warp) {
+            B_HIP(hipMalloc((void **)&b->d_wsrc, wsrc_bytes));
+            B_HIP(hipMalloc((void **)&b->d_wp_jobs, warp_jobs_bytes(b)));
+            b->wp_dirty = true;
+        }
+        const bool rs_tensor = tensor && !b->warp;  // (a warp: the resample's jobs are the u8 ones, the warp writes the tensor)
         if (tensor) {  // (the table of four channels: every image looks up its own first ncomp rows)
-            if (b->placed) B_HIP(hipMalloc((void **)&b->d_ptn_jobs, (size_t)n_images * sizeof(PlacedTensorJob)));
-            else B_HIP(hipMalloc((void **)&b->d_tn_jobs, (size_t)n_images * 2u * sizeof(TensorJob)));
             B_HIP(hipMalloc(&b->d_tn_table, TN_TABLE_MAX));
             std::vector<uint32_t> table(TN_TABLE_MAX / 4u, 0u);
             uint32_t nc_max = rgb ? 3u : 1u;
             for (uint32_t i = 0; i < n_images && !rgb; i++) nc_max = std::max<uint32_t>(nc_max, b->descs[i].ncomp);
             tensor_table(tensor->dtype, tensor->mean, tensor->std, nc_max, table.data());
             B_HIP(hipMemcpy(b->d_tn_table, table.data(), TN_TABLE_MAX, hipMemcpyHostToDevice));
+        }
+        if (rs_tensor && b->placed) {
+            B_HIP(hipMalloc((void **)&b->d_ptn_jobs, (size_t)n_images * sizeof(PlacedTensorJob)));
+        } else if (rs_tensor) {
+            B_HIP(hipMalloc((void **)&b->d_tn_jobs, (size_t)n_images * 2u * sizeof(TensorJob)));
         } else if (b->placed) {
             B_HIP(hipMalloc((void **)&b->d_pl_jobs, (size_t)n_images * sizeof(PlacedJob)));
         } else {
@@ -495,7 +556,39 @@ int jpgpu_batch_set_flips(jpgpu_batch *b, const uint8_t *flips) {
     if (!b) return JPGPU_ERR_FORMAT;
     if (!b->tn_es) return set_err(b->err, JPGPU_ERR_UNSUPPORTED, "jpgpu_batch_set_flips: the batch has no tensor format");
     for (size_t i = 0; i < b->tn_flips.size(); i++) b->tn_flips[i] = flips && flips[i] ? 1 : 0;
-    b->tn_dirty = true;
+    if (b->warp) b->wp_dirty = true;  // (a warped batch: the flip is a field of the WarpJobs)
+    else b->tn_dirty = true;
+    return JPGPU_OK;
+}
+int jpgpu_batch_create_warped(int device, const jpgpu_image_desc *descs, const jpgpu_window *windows, const jpgpu_placement *placements,
+                              const uint8_t *fill, uint16_t out_w, uint16_t out_h, const jpgpu_tensor_format *format, const jpgpu_warp_options *warp,
+                              uint32_t n_images, uint32_t flags, jpgpu_batch **out) {
+    if (!warp) return jpgpu_batch_create_placed(device, descs, windows, placements, fill, out_w, out_h, format, n_images, flags, out);
+    if (out_w == 0 || out_h == 0) {  // (0, 0 would mean "none" below: refuse it here)
+        if (!out) return JPGPU_ERR_FORMAT;
+        jpgpu_batch *b = new jpgpu_batch();
+        *out = b;
+        return set_err(b->err, JPGPU_ERR_FORMAT, "a warp needs an output size (%ux%u: width and height must be 1..%u)", out_w, out_h, RS_MAX_OUT);
+    }
+    return batch_create(device, descs, windows, out_w, out_h, format, n_images, flags, out, placements, fill, warp);
+}
+int jpgpu_batch_set_warps(jpgpu_batch *b, const jpgpu_warp *warps) {
+    if (!b) return JPGPU_ERR_FORMAT;
+    if (!b->warp) return set_err(b->err, JPGPU_ERR_UNSUPPORTED, "jpgpu_batch_set_warps: the batch has no warp (jpgpu_batch_create_warped)");
+    for (size_t i = 0; warps && i < b->wp_m.size(); i++)  // (one refused matrix refuses the call: nothing is changed)
+        if (!warp_check(warps[i].m, b->rs_w, b->rs_h))
+            return set_err(b->err, JPGPU_ERR_FORMAT, "jpgpu_batch_set_warps: image %zu: matrix (%g, %g, %g, %g, %g, %g) refused for %ux%u (jpgpu_warp_check)", i,
+                           warps[i].m[0], warps[i].m[1], warps[i].m[2], warps[i].m[3], warps[i].m[4], warps[i].m[5], b->rs_w, b->rs_h);
+    for (size_t i = 0; i < b->wp_m.size(); i++) b->wp_m[i] = warps ? warps[i] : jpgpu_warp{{1.0, 0.0, 0.0, 0.0, 1.0, 0.0}};
+    b->wp_dirty = true;
+    return JPGPU_OK;
+}
+int jpgpu_warp_check(const jpgpu_warp *warp, uint32_t out_w, uint32_t out_h) {
+    return (warp && out_w && out_h && warp_check(warp->m, out_w, out_h)) ? JPGPU_OK : JPGPU_ERR_FORMAT;
+}
+int jpgpu_warp_nearest_axis(double a, double b, uint32_t out_size, int32_t *idx) {
+    if (!idx && out_size) return JPGPU_ERR_FORMAT;
+    warp_nearest_axis(a, b, out_size, idx);
     return JPGPU_OK;
 }
 
@@ -514,6 +607,10 @@ void jpgpu_batch_destroy(jpgpu_batch *b) {
         if (b->d_pl_jobs) hipFree(b->d_pl_jobs);
         if (b->d_ptn_jobs) hipFree(b->d_ptn_jobs);
         if (b->h_ptn_jobs) hipHostFree(b->h_ptn_jobs);
+        if (b->d_wsrc) hipFree(b->d_wsrc);
+        if (b->d_wp_jobs) hipFree(b->d_wp_jobs);
+        if (b->h_wp_jobs) hipHostFree(b->h_wp_jobs);
+        if (b->wp_sent) hipEventDestroy(b->wp_sent);
         if (b->d_tn_table) hipFree(b->d_tn_table);
         if (b->h_tn_jobs) hipHostFree(b->h_tn_jobs);
         if (b->tn_sent) hipEventDestroy(b->tn_sent);
@@ -992,19 +1089,26 @@ int jpgpu_batch_decode(jpgpu_batch *b, void *hip_stream) {
                                  b->win.lds_bytes, b->win.scales, s));
     if (b->tn_es && b->tn_sent) B_HIP(hipStreamWaitEvent(s, b->tn_sent, 0));  // (the jobs may have gone up on another stream than this one)
     const bool rgb_out = (b->flags & JPGPU_BATCH_RGB_OUTPUT) != 0;
-    if (b->placed && b->tn_es)  // (placements: the kernels of placed.hip, for this batch only)
+    const bool rs_tensor = b->tn_es && !b->warp;  // (a warped batch resamples to u8, whatever it writes in the end)
+    if (b->placed && rs_tensor)  // (placements: the kernels of placed.hip, for this batch only)
         B_HIP(launch_resample_placed_tensor(b->d_ptn_jobs, b->d_rs_tab, b->d_tn_table, b->tn_es, (uint32_t)b->descs.size(), b->rs_max_bands, b->rs_lds_bytes, s, rgb_out));
     else if (b->placed)
         B_HIP(launch_resample_placed(b->d_pl_jobs, b->d_rs_tab, (uint32_t)b->descs.size(), b->rs_max_bands, b->rs_lds_bytes, s, rgb_out));
-    else if (b->tn_es)  // (a tensor output: the same resample, its vertical pass writes every image's tensor)
+    else if (rs_tensor)  // (a tensor output: the same resample, its vertical pass writes every image's tensor)
         B_HIP(launch_resample_tensor(b->d_tn_jobs, b->d_rs_tab, b->d_tn_table, b->tn_es, (uint32_t)b->descs.size(), b->rs_max_bands, b->rs_lds_bytes, s,
                                       (b->flags & JPGPU_BATCH_RGB_OUTPUT) != 0));
     else if (b->rs_w)  // (an output size: every image's pixels, wherever the launches above left them in the intermediate arena)
         B_HIP(launch_resample_band(b->d_rs_jobs, b->d_rs_tab, (uint32_t)b->descs.size(), b->rs_max_bands, b->rs_lds_bytes, s, (b->flags & JPGPU_BATCH_RGB_OUTPUT) != 0));
     if (b->rs_max_runs && !b->placed) {  // (the images whose bands go in runs: their own launch, beside the band launch above)
         const uint32_t n_rs = (uint32_t)b->descs.size();
-        if (b->tn_es) B_HIP(launch_resample_tensor_run(b->d_tn_jobs + n_rs, b->d_rs_tab, b->d_tn_table, b->d_rs_bpr, b->tn_es, n_rs, b->rs_max_runs, b->rs_lds_bytes, s));
+        if (rs_tensor) B_HIP(launch_resample_tensor_run(b->d_tn_jobs + n_rs, b->d_rs_tab, b->d_tn_table, b->d_rs_bpr, b->tn_es, n_rs, b->rs_max_runs, b->rs_lds_bytes, s));
         else B_HIP(launch_resample_run(b->d_rs_jobs + n_rs, b->d_rs_tab, b->d_rs_bpr, n_rs, b->rs_max_runs, b->rs_lds_bytes, s));
+    }
+    if (b->warp) {  // (the warp: behind the resample on the same stream, from the second intermediate arena into the output arena)
+        const uint32_t tiles = (b->rs_w * b->rs_h + WP_NT - 1u) / WP_NT;
+        const int32_t *tabs = reinterpret_cast<const int32_t *>(b->d_wp_jobs + b->descs.size() * sizeof(WarpJob));
+        if (b->wp_sent) B_HIP(hipStreamWaitEvent(s, b->wp_sent, 0));  // (the jobs may have gone up on another stream than this one)
+        B_HIP(launch_warp(reinterpret_cast<const WarpJob *>(b->d_wp_jobs), tabs, b->d_tn_table, b->tn_es, (uint32_t)b->descs.size(), tiles, s));
     }
     if (b->phase_events_valid) B_HIP(hipEventRecord(b->ev_phase[5], s));
     B_HIP(batch_mark_enqueued(b, s));

@@ -22,6 +22,7 @@
 #include "resample_band.hpp"
 #include "tensor_band.hpp"
 #include "placed_band.hpp"
+#include "warp_band.hpp"
 #include "window_band.hpp"
 
 using namespace jpgpu;
@@ -160,6 +161,20 @@ struct jpgpu_batch {
     PlacedJob *d_pl_jobs = nullptr;
     PlacedTensorJob *d_ptn_jobs = nullptr;
     PlacedTensorJob *h_ptn_jobs = nullptr;  // pinned mirror, as h_tn_jobs
+    // A warp (jpgpu_batch_create_warped, warp_band.hpp; warp == false: none): the resample launch is the u8 one of the same arguments —
+    // band, run or placed, whatever tn_es says — and writes a second intermediate arena the batch owns (d_wsrc, wsrc_off: rs_h x rs_w x nc
+    // bytes per image); one launch behind it reads that arena through every image's matrix and writes the output arena, pixels or (tn_es)
+    // tensors.  The WarpJobs and the N-sep tables behind them ([n WarpJob | n x (rs_w + rs_h) int32]) travel from a pinned mirror on the
+    // decode's stream, as the TensorJobs do: fresh matrices and flips come with every call of a loader.
+    bool warp = false;
+    uint32_t wp_filter = 0;            // JPGPU_WARP_*
+    uint32_t wp_fill = 0;              // wfill[c] in byte c
+    std::vector<jpgpu_warp> wp_m;      // per image (jpgpu_batch_set_warps)
+    bool wp_dirty = false;             // matrices or flips changed: the WarpJobs go up before the next decode
+    std::vector<size_t> wsrc_off;
+    uint8_t *d_wsrc = nullptr;
+    uint8_t *d_wp_jobs = nullptr, *h_wp_jobs = nullptr;
+    hipEvent_t wp_sent = nullptr;      // behind the last copy out of the mirror
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
     // Behind the last work enqueued on a caller's stream that reads the batch's tables or its coefficient arena (every decode,
     // jpgpu_batch_classify_on_device).  That stream may be a non-blocking one, which a blocking copy on the null stream does not order

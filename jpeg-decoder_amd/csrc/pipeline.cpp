@@ -25,6 +25,7 @@
 #include "host/frontend.hpp"
 #include "host_common.hpp"
 #include "tensor_band.hpp"
+#include "warp_band.hpp"
 
 using jpgpu::host::DecodeError;
 using jpgpu::host::Frontend;
@@ -266,6 +267,9 @@ struct SubBatch {
     bool fit_on = false;              // created with placements under this rule (jpgpu_pipeline_set_fit)
     jpgpu_fit fit{};
     std::vector<jpgpu_placement> pls; // ... the placement of every image as the batch holds it
+    bool warp_on = false;             // created with these warp options (jpgpu_pipeline_set_warp)
+    jpgpu_warp_options warp_opt{};
+    std::vector<jpgpu_warp> warps;    // ... the matrix of every image as the batch holds it (jpgpu_batch_set_warps)
     uint32_t remaining = 0;  // images not yet uploaded / failed (uploader thread only)
     hipEvent_t ready[kCopyStreams] = {nullptr, nullptr, nullptr, nullptr};
     hipEvent_t decoded = nullptr;  // recorded on the compute stream behind the sub-batch's pixel kernels: downloads and the gather wait for it
@@ -287,6 +291,9 @@ struct SubBatch {
         fit_on = false;
         fit = jpgpu_fit{};
         pls.clear();
+        warp_on = false;
+        warp_opt = jpgpu_warp_options{};
+        warps.clear();
     }
 };
 
@@ -333,6 +340,8 @@ struct jpgpu_pipeline {
     uint32_t filter = 0;            // jpgpu_pipeline_set_filter (JPGPU_FILTER_*; 0: bilinear)
     bool fit_on = false;            // jpgpu_pipeline_set_fit (a rule other than stretch)
     jpgpu_fit fit{};
+    bool warp_on = false;           // jpgpu_pipeline_set_warp
+    jpgpu_warp_options warp_opt{};
     jpgpu_tensor_format tn{};
     int color_transform = -1;       // jpgpu_pipeline_set_color_transform (< 0: what every image says itself)
     size_t max_bytes = SIZE_MAX;    // jpgpu_pipeline_set_max_decoding_buffer_size
@@ -366,7 +375,7 @@ static const jpgpu_pipeline *child_of(const jpgpu_pipeline *p, uint32_t &image) 
     image /= n;
     return c;
 }
-static int multi_decode(jpgpu_pipeline *p, const uint8_t *const *data, const size_t *len, const jpgpu_window *windows, const uint8_t *flips, uint32_t n,
+static int multi_decode(jpgpu_pipeline *p, const uint8_t *const *data, const size_t *len, const jpgpu_window *windows, const uint8_t *flips, const jpgpu_warp *warps, uint32_t n,
                         uint32_t flags);
 // Up to how many scans does a call walk its progressive frames a WAVE per scan (pipelined, huff_prog_job.hpp)?  Always: the launch
 // order keeps a frame's waves on one XCD, producers in front (csrc/batch_entropy.cpp), so an oversubscribed launch cannot starve a producer
@@ -645,6 +654,11 @@ int jpgpu_pipeline_decode_windowed(jpgpu_pipeline *p, const uint8_t *const *data
 
 int jpgpu_pipeline_decode_augmented(jpgpu_pipeline *p, const uint8_t *const *data, const size_t *len, const jpgpu_window *windows, const uint8_t *flips,
                                     uint32_t n, uint32_t flags) {
+    return jpgpu_pipeline_decode_warped(p, data, len, windows, flips, nullptr, n, flags);
+}
+
+int jpgpu_pipeline_decode_warped(jpgpu_pipeline *p, const uint8_t *const *data, const size_t *len, const jpgpu_window *windows, const uint8_t *flips,
+                                 const jpgpu_warp *warps, uint32_t n, uint32_t flags) {
     jpgpu::TraceRange roctx_range("jpgpu_pipeline_decode");
     // (unknown bits are refused, not ignored: 8u was round 2-3's JPGPU_PIPELINE_PROGRESSIVE_DELTAS, removed in round 4 — a caller built
     // against that header would otherwise silently get another transport: ADVICE r4)
@@ -657,7 +671,9 @@ int jpgpu_pipeline_decode_augmented(jpgpu_pipeline *p, const uint8_t *const *dat
     if (p && p->filter && !p->rs_w) return jpgpu::set_err(p->err, JPGPU_ERR_FORMAT, "jpgpu_pipeline_decode: a resample filter needs an output size (jpgpu_pipeline_set_output_size)");
     if (p && p->fit_on && !p->rs_w) return jpgpu::set_err(p->err, JPGPU_ERR_FORMAT, "jpgpu_pipeline_decode: a fit needs an output size (jpgpu_pipeline_set_output_size)");
     if (p && flips && !p->tensor) return jpgpu::set_err(p->err, JPGPU_ERR_FORMAT, "jpgpu_pipeline_decode_augmented: flips need a tensor output (jpgpu_pipeline_set_tensor_output)");
-    if (p && !p->children.empty()) return (n && (!data || !len)) ? JPGPU_ERR_FORMAT : multi_decode(p, data, len, windows, flips, n, flags);
+    if (p && p->warp_on && !p->rs_w) return jpgpu::set_err(p->err, JPGPU_ERR_FORMAT, "jpgpu_pipeline_decode: a warp needs an output size (jpgpu_pipeline_set_output_size)");
+    if (p && warps && !p->warp_on) return jpgpu::set_err(p->err, JPGPU_ERR_FORMAT, "jpgpu_pipeline_decode_warped: warps need warp options (jpgpu_pipeline_set_warp)");
+    if (p && !p->children.empty()) return (n && (!data || !len)) ? JPGPU_ERR_FORMAT : multi_decode(p, data, len, windows, flips, warps, n, flags);
     if (!p || !p->pool || (n && (!data || !len))) return JPGPU_ERR_FORMAT;
     if ((flags & JPGPU_PIPELINE_GATHER) && !p->gather_on) flags &= ~(uint32_t)JPGPU_PIPELINE_GATHER;  // (one device: the pixels are where a gather would put them)
     int rc = jpgpu::use_device(p->device, p->err);
@@ -771,6 +787,13 @@ int jpgpu_pipeline_decode_augmented(jpgpu_pipeline *p, const uint8_t *const *dat
                     p->places[i] = jpgpu_placement{0, 0, 0, 0};
                     throw DecodeError{JPGPU_ERR_FORMAT, msg};
                 }
+                // (a matrix the warp refuses fails the image alone, like a refused window)
+                if (p->warp_on && warps && !jpgpu::warp_check(warps[i].m, p->rs_w, p->rs_h)) {
+                    char msg[240];
+                    snprintf(msg, sizeof msg, "warp: matrix (%g, %g, %g, %g, %g, %g) refused for %ux%u (jpgpu_warp_check)", warps[i].m[0], warps[i].m[1], warps[i].m[2],
+                             warps[i].m[3], warps[i].m[4], warps[i].m[5], p->rs_w, p->rs_h);
+                    throw DecodeError{JPGPU_ERR_FORMAT, msg};
+                }
                 const char *bad = nullptr;  // (the format's means and stds against THIS image's channels)
                 if (p->tensor && !jpgpu::tensor_format_ok(p->tn.dtype, p->tn.reserved, p->tn.mean, p->tn.std, p->rgb ? 3u : d.ncomp, bad))
                     throw DecodeError{JPGPU_ERR_FORMAT, std::string("tensor format: ") + bad};
@@ -876,6 +899,7 @@ int jpgpu_pipeline_decode_augmented(jpgpu_pipeline *p, const uint8_t *const *dat
         std::vector<jpgpu_window> wins;  // (stays empty when no image of the sub-batch has a window: jpgpu_batch_create's own path)
         std::vector<uint8_t> fl;         // a tensor output: every image's flip
         std::vector<jpgpu_placement> pls;  // a fit: every image's placement
+        std::vector<jpgpu_warp> wm;        // a warp: every image's matrix
         bool sub_windowed = false;
         for (uint32_t k = first; any_window && k < last; k++) sub_windowed = sub_windowed || win[ok[k]].w != 0;
         for (uint32_t k = first; k < last; k++) {
@@ -885,6 +909,7 @@ int jpgpu_pipeline_decode_augmented(jpgpu_pipeline *p, const uint8_t *const *dat
             if (sub_windowed) wins.push_back(win[ok[k]]);
             if (p->tensor) fl.push_back(flips && flips[ok[k]] ? 1 : 0);
             if (p->fit_on) pls.push_back(p->places[ok[k]]);
+            if (p->warp_on) wm.push_back(warps ? warps[ok[k]] : jpgpu_warp{{1.0, 0.0, 0.0, 0.0, 1.0, 0.0}});
         }
         sb.remaining = last - first;
         // Sub-batches of device-entropy images need no pinned staging for coefficients (their entropy-coded bytes are staged by
@@ -897,6 +922,8 @@ int jpgpu_pipeline_decode_augmented(jpgpu_pipeline *p, const uint8_t *const *dat
         // (... or another fit: the batch is placed or not, and holds the fill, for its lifetime)
         reuse = reuse && sb.filter == p->filter;  // (... or another filter: other tables throughout)
         reuse = reuse && sb.fit_on == p->fit_on && (!p->fit_on || memcmp(&sb.fit, &p->fit, sizeof(jpgpu_fit)) == 0);
+        // (... or other warp options: the batch has a warp stage or not, and holds its filter and fill, for its lifetime)
+        reuse = reuse && sb.warp_on == p->warp_on && (!p->warp_on || memcmp(&sb.warp_opt, &p->warp_opt, sizeof(jpgpu_warp_options)) == 0);
         const bool same_pls = pls.size() == sb.pls.size() && (pls.empty() || memcmp(pls.data(), sb.pls.data(), pls.size() * sizeof(jpgpu_placement)) == 0);
         for (size_t k = 0; reuse && k < descs.size(); k++) reuse = same_geometry(descs[k], sb.descs[k]);
         // ... and the same windows: the window group's geometry and the output offsets are made from them (a kept batch with other
@@ -918,7 +945,9 @@ int jpgpu_pipeline_decode_augmented(jpgpu_pipeline *p, const uint8_t *const *dat
             sb.drop();
             const uint32_t bf = (p->rgb ? JPGPU_BATCH_RGB_OUTPUT : JPGPU_BATCH_DEFAULT) |  // (every image three channels: the batch's resample converts)
                                 JPGPU_BATCH_FILTER(p->filter);                             // (0 without an output size: checked above)
-            rc = p->fit_on ? jpgpu_batch_create_placed(p->device, descs.data(), wins.empty() ? nullptr : wins.data(), pls.data(), p->fit.fill, p->rs_w, p->rs_h,
+            rc = p->warp_on ? jpgpu_batch_create_warped(p->device, descs.data(), wins.empty() ? nullptr : wins.data(), p->fit_on ? pls.data() : nullptr, p->fit.fill, p->rs_w,
+                                                        p->rs_h, p->tensor ? &p->tn : nullptr, &p->warp_opt, (uint32_t)descs.size(), bf, &sb.batch)
+                 : p->fit_on ? jpgpu_batch_create_placed(p->device, descs.data(), wins.empty() ? nullptr : wins.data(), pls.data(), p->fit.fill, p->rs_w, p->rs_h,
                                                        p->tensor ? &p->tn : nullptr, (uint32_t)descs.size(), bf, &sb.batch)
                  : p->tensor ? jpgpu_batch_create_tensor(p->device, descs.data(), wins.empty() ? nullptr : wins.data(), p->rs_w, p->rs_h, &p->tn, (uint32_t)descs.size(), bf, &sb.batch)
                  : p->rs_w ? jpgpu_batch_create_resized(p->device, descs.data(), wins.empty() ? nullptr : wins.data(), p->rs_w, p->rs_h, (uint32_t)descs.size(), bf, &sb.batch)
@@ -944,6 +973,8 @@ int jpgpu_pipeline_decode_augmented(jpgpu_pipeline *p, const uint8_t *const *dat
             sb.filter = p->filter;
             sb.fit_on = p->fit_on, sb.fit = p->fit, sb.pls = pls;
             sb.flips.assign(descs.size(), 0);
+            sb.warp_on = p->warp_on, sb.warp_opt = p->warp_opt;
+            sb.warps.assign(p->warp_on ? descs.size() : 0, jpgpu_warp{{1.0, 0.0, 0.0, 0.0, 1.0, 0.0}});
             sb.compact = compact;
             sb.h_coef_bytes = jpgpu_batch_coef_arena_bytes(sb.batch);
             if (compact) {  // worst-case compact size per component (12 B/block more than dense), 256-B aligned
@@ -963,6 +994,12 @@ int jpgpu_pipeline_decode_augmented(jpgpu_pipeline *p, const uint8_t *const *dat
             rc = jpgpu_batch_set_flips(sb.batch, fl.data());
             if (rc) return jpgpu::set_err(p->err, rc, "%s", jpgpu_batch_last_error(sb.batch));
             sb.flips = fl;
+        }
+        // (other matrices, kept or new: set in place like the flips — fields of the job records)
+        if (p->warp_on && memcmp(wm.data(), sb.warps.data(), wm.size() * sizeof(jpgpu_warp)) != 0) {
+            rc = jpgpu_batch_set_warps(sb.batch, wm.data());
+            if (rc) return jpgpu::set_err(p->err, rc, "%s", jpgpu_batch_last_error(sb.batch));
+            sb.warps = wm;
         }
         if (download && (!sb.h_out || sb.h_out_bytes < jpgpu_batch_out_arena_bytes(sb.batch))) {
             if (sb.h_out) (void)hipHostFree(sb.h_out);
@@ -1508,6 +1545,15 @@ int jpgpu_pipeline_set_fit(jpgpu_pipeline *p, const jpgpu_fit *fit) {
     p->fit = p->fit_on ? *fit : jpgpu_fit{};
     return JPGPU_OK;
 }
+int jpgpu_pipeline_set_warp(jpgpu_pipeline *p, const jpgpu_warp_options *warp) {
+    if (!p) return JPGPU_ERR_FORMAT;
+    if (warp && (warp->filter > JPGPU_WARP_BILINEAR || warp->reserved != 0))
+        return jpgpu::set_err(p->err, JPGPU_ERR_FORMAT, "warp options: filter %u, reserved %u (JPGPU_WARP_NEAREST or JPGPU_WARP_BILINEAR, reserved 0)", warp->filter, warp->reserved);
+    for (jpgpu_pipeline *c : p->children) jpgpu_pipeline_set_warp(c, warp);
+    p->warp_on = warp != nullptr;
+    p->warp_opt = warp ? *warp : jpgpu_warp_options{};
+    return JPGPU_OK;
+}
 int jpgpu_pipeline_image_placement(const jpgpu_pipeline *p, uint32_t i, jpgpu_placement *out) {
     MULTI(p, i, jpgpu_pipeline_image_placement(c, ci, out), JPGPU_ERR_FORMAT)
     if (!p || i >= p->n || !out || i >= p->places.size() || p->places[i].rw == 0 || p->places[i].rh == 0) return JPGPU_ERR_FORMAT;
@@ -1764,7 +1810,7 @@ int jpgpu_pipeline_last_timings(const jpgpu_pipeline *p, jpgpu_pipeline_timings 
 // copy of one sub-batch runs while the next ones decode; nothing to reduce — SURVEY 8e); jpgpu_pipeline_pixels_device then points
 // into the copies.  gather_ms = what the call still waited for the copies after the last child had decoded (the exposed part),
 // gather_copy_ms = the longest child's summed copy time (events around each copy).
-static int multi_decode(jpgpu_pipeline *p, const uint8_t *const *data, const size_t *len, const jpgpu_window *windows, const uint8_t *flips, uint32_t n,
+static int multi_decode(jpgpu_pipeline *p, const uint8_t *const *data, const size_t *len, const jpgpu_window *windows, const uint8_t *flips, const jpgpu_warp *warps, uint32_t n,
                         uint32_t flags) {
     const double t0 = now_ms(), cpu0 = process_cpu_ms();
     const uint32_t nc = (uint32_t)p->children.size();
@@ -1779,11 +1825,13 @@ static int multi_decode(jpgpu_pipeline *p, const uint8_t *const *data, const siz
     std::vector<std::vector<size_t>> cl(nc);
     std::vector<std::vector<jpgpu_window>> cw(nc);
     std::vector<std::vector<uint8_t>> cf(nc);
+    std::vector<std::vector<jpgpu_warp>> cm(nc);
     for (uint32_t i = 0; i < n; i++) {
         cd[i % nc].push_back(data[i]);
         cl[i % nc].push_back(len[i]);
         if (windows) cw[i % nc].push_back(windows[i]);
         if (flips) cf[i % nc].push_back(flips[i]);
+        if (warps) cm[i % nc].push_back(warps[i]);
     }
     std::vector<int> rcs(nc, JPGPU_OK);
     std::vector<std::thread> th;
@@ -1792,8 +1840,8 @@ static int multi_decode(jpgpu_pipeline *p, const uint8_t *const *data, const siz
         p->children[k]->gather_device = p->device;
         th.emplace_back([&, k] {
             pin_to(p->child_cpus[k]);  // (the call's uploader thread starts from here and inherits the mask)
-            rcs[k] = jpgpu_pipeline_decode_augmented(p->children[k], cd[k].data(), cl[k].data(), windows ? cw[k].data() : nullptr, flips ? cf[k].data() : nullptr,
-                                                     (uint32_t)cd[k].size(), child_flags);
+            rcs[k] = jpgpu_pipeline_decode_warped(p->children[k], cd[k].data(), cl[k].data(), windows ? cw[k].data() : nullptr, flips ? cf[k].data() : nullptr,
+                                                  warps ? cm[k].data() : nullptr, (uint32_t)cd[k].size(), child_flags);
         });
     }
     for (auto &t : th) t.join();

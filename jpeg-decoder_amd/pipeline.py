@@ -9,7 +9,7 @@ import ctypes as C
 import numpy as np
 
 from . import _native as N
-from .batch import filter_id, flip_bytes, output_size_pair, window_structs
+from .batch import filter_id, flip_bytes, output_size_pair, warp_structs, window_structs
 from .decoder import CODING_PROCESSES, PIXEL_FORMATS, ImageInfo
 from .error import check, error_for_status
 from .worker import color_transform_id
@@ -76,7 +76,7 @@ class Pipeline:
 
     def decode(self, streams, download=True, dense=False, device_entropy=True, scale=None, color_transform=None, max_decoding_buffer_size=None,
                gather=False, host_light=None, input_pinned=False, progressive_on_host=False, windows=None, output_size=None,
-               tensor=None, flips=None, rgb=False, fit=None, filter=None):
+               tensor=None, flips=None, rgb=False, fit=None, filter=None, warp=None, warps=None):
         """-> list with, per stream, a numpy uint8 array of the decoded pixels (``Decoder.decode()``'s Vec<u8>) or the
         ``Error`` instance that stream produced.  download=False leaves the pixels in HBM (see ``device_pointer``); dense=True sends all
         64 coefficients of every block over PCIe instead of the compact form (same pixels, A/B switch); device_entropy=True
@@ -116,7 +116,13 @@ class Pipeline:
         filter: None or "bilinear" (the default), "box", "hamming", "bicubic", "lanczos", or a JPGPU_FILTER_* id (jpgpu_pipeline_set_filter,
         set on every call; any other than bilinear needs output_size, else FormatError and nothing is decoded; an id the library does not
         know: FormatError): every resample is Pillow's ``Image.resize(size, F)`` with that filter — CLIP's transform is
-        ``fit=Fit("shorter_side_crop", size=224), output_size=(224, 224), filter="bicubic"``."""
+        ``fit=Fit("shorter_side_crop", size=224), output_size=(224, 224), filter="bicubic"``.
+        warp: None or a ``WarpOptions`` (jpgpu_pipeline_set_warp, set on every call; needs output_size, else FormatError and nothing is
+        decoded): a warp stage behind the output size — Pillow's ``Image.transform(size, Image.AFFINE, m, NEAREST or BILINEAR,
+        fillcolor=warp.fill)`` of every stream's u8 result, mirrored first when the stream is flipped.
+        warps: None (identities) or a list with six coefficients or None per stream (needs `warp`, else FormatError and nothing is
+        decoded); a matrix the library refuses fails its stream alone.  Fresh matrices for the same files keep the pipeline's
+        sub-batches, like windows and flips."""
         if isinstance(streams, PinnedFiles):
             bufs = None
             n = len(streams)
@@ -128,6 +134,7 @@ class Pipeline:
         wins = window_structs(windows, n)  # (raises on a list of the wrong length, before anything native is called)
         size = (0, 0) if output_size is None else output_size_pair(output_size)
         flip_arr = flip_bytes(flips, n)
+        warp_arr = warp_structs(warps, n)
         filt = filter_id(filter)
         fmt = None if tensor is None else tensor.struct()
         self._shape = None if tensor is None else (tensor.numpy_dtype, size[1], size[0])
@@ -145,6 +152,9 @@ class Pipeline:
         fit_s = None if fit is None else fit.struct()
         st = L.jpgpu_pipeline_set_fit(self._h, None if fit_s is None else C.byref(fit_s))
         check(st, L.jpgpu_pipeline_last_error(self._h) if st else b"")
+        warp_s = None if warp is None else warp.struct()
+        st = L.jpgpu_pipeline_set_warp(self._h, None if warp_s is None else C.byref(warp_s))
+        check(st, L.jpgpu_pipeline_last_error(self._h) if st else b"")
         if bufs is None:
             ptrs = (C.c_void_p * max(n, 1))(*[streams.base + o for o in streams.offsets])
             lens = (C.c_size_t * max(n, 1))(*streams.lengths)
@@ -155,7 +165,9 @@ class Pipeline:
         flags = ((N.PIPELINE_DOWNLOAD if download else 0) | (N.PIPELINE_DENSE if dense else 0) | (N.PIPELINE_DEVICE_ENTROPY if device_entropy else 0) |
                  (N.PIPELINE_GATHER if gather else 0) | (N.PIPELINE_INPUT_PINNED if input_pinned else 0) | (N.PIPELINE_PROGRESSIVE_ON_HOST if progressive_on_host else 0) |
                  (0 if host_light is None else (N.PIPELINE_HOST_LIGHT if host_light else N.PIPELINE_HOST_STAGED)))
-        if flip_arr is not None:
+        if warp_arr is not None or warp is not None:
+            st = L.jpgpu_pipeline_decode_warped(self._h, C.cast(ptrs, C.POINTER(C.c_void_p)), lens, wins, flip_arr, warp_arr, n, flags)
+        elif flip_arr is not None:
             st = L.jpgpu_pipeline_decode_augmented(self._h, C.cast(ptrs, C.POINTER(C.c_void_p)), lens, wins, flip_arr, n, flags)
         elif wins is None:
             st = L.jpgpu_pipeline_decode(self._h, C.cast(ptrs, C.POINTER(C.c_void_p)), lens, n, flags)
