@@ -272,6 +272,61 @@ def test_runs_of_bands(name):
     assert np.array_equal(outs[0], want_u8(f, gray[0], gray[1], None, size, rgb=True).reshape(-1))
 
 
+@pytest.mark.parametrize("name", WIDE)
+def test_cmyk_on_the_run_route(name):
+    """resample_run_body<4>: a CMYK 64 x 1080 source under RGB output to (224, 225) — the converting horizontal pass over the rows a run's
+    bands do not share — as bytes and as f32 / f16 / bf16 tensors, flipped and not.  The conversion comes first: resampling the four
+    inks and converting afterwards gives other bytes (asserted)."""
+    f = F.NAMES[name]
+    size = (224, 225)
+    case, full = block_case("cmyk444", 64, 1080, 2, 1)
+    rb, bands, cap, spans = plan_of(name, 1080, 224, 225, 3)
+    assert bands >= 2 and all(s1 - s0 <= cap for s0, s1 in spans) and sum(s1 - s0 for s0, s1 in spans) / (spans[-1][1] - spans[0][0]) > ROLL_MIN, (rb, bands)
+    sums = []
+    want = want_u8(f, case, full, None, size, rgb=True, sums=sums)
+    assert clamps_at_both_ends(sums), sums
+    assert not np.array_equal(want, G.to_rgb(F.resize(RZ.source_of(case, full, None), 224, 225, f)))
+    outs, path = decode([case], None, size, name, rgb=True)
+    assert path.endswith("+rgb+resize:" + name + "+roll"), path
+    assert np.array_equal(outs[0], want.reshape(-1)), np.nonzero(outs[0] != want.reshape(-1))[0][:10].tolist()
+    for dtype in ("float32", "float16", "bfloat16"):
+        fmt, ref_fmt = TN.fmt_of(dtype)
+        outs, path = decode([case, case], None, size, name, fmt, [True, False], rgb=True)
+        assert path.endswith("+rgb+resize:" + name + "+tensor+roll"), path
+        for i, o in enumerate(outs):
+            assert np.array_equal(T.bits(o), T.bits(T.to_tensor(want, T.table(ref_fmt, 3), i == 0))), (name, dtype, i)
+
+
+@pytest.mark.parametrize("name", WIDE)
+def test_forced_run_routes_give_the_band_route_s_bytes(monkeypatch, name):
+    """JPGPU_RS_ROLL = 2 / 4 / 8 sends every candidate down the run route: the 97 x 61 image to (224, 225), which keeps its four bands by
+    the rule (its rows overlap too little), decoded under each — plans the rule never picks, the bytes of knob `1`."""
+    f = F.NAMES[name]
+    size = (224, 225)
+    cases = [block_case("420", 97, 61), block_case("gray", 97, 61), block_case("cmyk444", 97, 61)]  # (under RGB output: src_nc 0, 1 and 4)
+    wins = None
+    _rb, bands, cap, sp = plan_of(name, 61, 224, 225, 3)  # (a candidate that does not roll by the rule)
+    assert bands >= 2 and all(s1 - s0 <= cap for s0, s1 in sp) and sum(s1 - s0 for s0, s1 in sp) / (sp[-1][1] - sp[0][0]) <= ROLL_MIN
+    wants = [want_u8(f, case, full, None, size, rgb=True) for case, full in cases]
+    fmt, ref_fmt = TN.fmt_of("float16")
+    flips = [True, False, True]
+    got = {}
+    for knob in ("1", "2", "4", "8", None):
+        if knob is None:
+            monkeypatch.delenv("JPGPU_RS_ROLL", raising=False)
+        else:
+            monkeypatch.setenv("JPGPU_RS_ROLL", knob)
+        outs, path = decode([c for c, _f in cases], wins, size, name, rgb=True)
+        assert path.endswith("+roll") == (knob in ("2", "4", "8")), (knob, path)
+        touts, tpath = decode([c for c, _f in cases], wins, size, name, fmt, flips, rgb=True)
+        assert tpath.endswith("+tensor+roll" if knob in ("2", "4", "8") else "+tensor"), (knob, tpath)
+        got[knob] = outs, touts
+        for i, (o, t) in enumerate(zip(outs, touts)):
+            assert np.array_equal(o, got["1"][0][i]) and np.array_equal(T.bits(t), T.bits(got["1"][1][i])), (name, knob, i)
+            assert np.array_equal(o, wants[i].reshape(-1)), (name, knob, i, np.nonzero(o != wants[i].reshape(-1))[0][:10].tolist())
+            assert np.array_equal(T.bits(t), T.bits(T.to_tensor(wants[i], T.table(ref_fmt, 3), flips[i]))), (name, knob, i)
+
+
 def test_bilinear_by_name_is_the_call_without_a_filter():
     cases = [block_case("420", 97, 61), block_case("gray", 97, 61)]
     wins = [(5, 3, 87, 55), None]

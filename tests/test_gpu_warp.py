@@ -10,6 +10,7 @@ import pytest
 import filter_ref as F
 import rgb_ref as G
 import tensor_ref as T
+import test_gpu_filters as FT
 import test_gpu_pipeline_windows as PW
 import test_gpu_resize as RZ
 import test_gpu_tensor as TN
@@ -32,6 +33,7 @@ def _load():
     PW.J = pkg
     RZ.J = pkg
     TN.J = pkg
+    FT.J = pkg
     assert J.device_count() >= 1, "no MI355X visible: the HIP path has no CPU fallback"
 
 
@@ -151,6 +153,42 @@ def test_rgb_output_warped():
     for i, o in enumerate(outs):
         u8 = want_of(resized_u8(cases[i], fulls[i], size, None, True, pls[i]), warps[i], "bilinear", flips[i])
         assert np.array_equal(T.bits(o), T.bits(T.to_tensor(u8, T.table(ref_fmt, 3), False))), i
+
+
+@pytest.mark.parametrize("filt", ["nearest", "bilinear"])
+def test_warp_behind_a_window_and_a_run_route(filt):
+    """The CMYK 64 x 1080 source of test_gpu_filters.test_cmyk_on_the_run_route, windowed at odd coordinates, under RGB output to
+    (224, 225): the run route in front of a rotation and a shear (rule N under NEAREST, rule B under BILINEAR).  `+roll` stands in
+    front of `+warp` in the path."""
+    size = (224, 225)
+    case, full = FT.block_case("cmyk444", 64, 1080, 2, 1)
+    wins = [(5, 3, 55, 1071), (1, 7, 61, 1069)]
+    warps = [WR.rotate_matrix(15, size), (1.0, 0.3, -4.0, 0.2, 1.0, 0.0)]
+    assert all(m[1] != 0.0 and m[3] != 0.0 for m in warps)  # (not the N-sep tables)
+    fmt, ref_fmt = TN.fmt_of("float16")
+    flips = [True, False]
+    for name in FT.WIDE:
+        for tensor in (None, fmt):
+            b = J.Batch([RZ._desc(case)] * 2, windows=wins, output_size=size, tensor=tensor, rgb=True, filter=name, warp=J.WarpOptions(filt, WFILL))
+            try:
+                RZ._upload(b, [case] * 2)
+                b.set_warps(warps)
+                if tensor is not None:
+                    b.set_flips(flips)
+                b.decode()
+                b.synchronize()
+                outs, path = [b.download(i) for i in range(2)], b.path
+            finally:
+                b.close()
+            assert ("+rgb+resize:" + name + "+roll+warp" + (":bilinear" if filt == "bilinear" else "")) in path and path.endswith("+tensor") == (tensor is not None), path
+            for i, o in enumerate(outs):
+                r = F.resize(G.to_rgb(RZ.source_of(case, full, wins[i])), size[0], size[1], F.NAMES[name])
+                want = want_of(r, warps[i], filt, flips[i] and tensor is not None)
+                assert not np.array_equal(want, r)
+                if tensor is None:
+                    assert np.array_equal(o, want.reshape(-1)), (name, filt, i, np.nonzero(o != want.reshape(-1))[0][:10].tolist())
+                else:
+                    assert np.array_equal(T.bits(o), T.bits(T.to_tensor(want, T.table(ref_fmt, 3), False))), (name, filt, i)
 
 
 def _nsep_matrix(w, h):

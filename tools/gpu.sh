@@ -166,6 +166,7 @@ for step in "$@"; do
       timeout 900 python tools/fuzz_gpu.py 65001 $n 2>&1 | tail -3 >> $O/fuzz.txt
       timeout 600 python tools/fuzz_gpu_worker.py 64001 $((n / 2 + 1)) 2>&1 | tail -3 >> $O/fuzz.txt
       timeout 600 python tools/fuzz_gpu_progressive.py 66001 $((n / 2 + 1)) 2>&1 | tail -3 >> $O/fuzz.txt
+      timeout 600 python tools/fuzz_gpu_output.py 67001 $((n / 4 + 1)) 2>&1 | tail -3 >> $O/fuzz.txt
       cat $O/fuzz.txt ;;
     latency)
       timeout 600 python tools/decoder_latency.py > $O/decoder_latency.txt 2>&1; tail -n 12 $O/decoder_latency.txt ;;
