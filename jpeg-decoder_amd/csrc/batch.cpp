@@ -6,101 +6,8 @@
 // and all output pixels.  One decode = a handful of launches over the whole batch.
 // Images of a fusable kind (4:2:0 YCbCr, 4:4:4 YCbCr / RGB, gray; any size) are grouped per kind and run the fused
 // kernels (fused.hip), one launch group per kind; everything else runs the generic two-kernel path (kernels.hip)
-// through device job tables.  jpgpu_batch_path names the kernels: "fused420", ..., "generic", or "mixed".
-#include <array>
-#include <map>
-
+// through device job tables.  jpgpu_batch_path names the kernels: "fused420", ..., "generic", or "mixed".  (An output size: batch_output.cpp.)
 #include "batch_internal.hpp"
-
-// The resample tables and bands of every image from its source size (its window's, else its output grid's): at creation and after
-// batch_rewindow.  Axes of equal (in, out) sizes share one table.
-static int batch_resample_tables(jpgpu_batch *b) {
-    const uint32_t n = (uint32_t)b->descs.size();
-    b->rs_jobs.assign(n, ResampleJob{});
-    b->rs_tab.clear();
-    b->rs_max_bands = b->rs_lds_bytes = b->rs_max_runs = 0;
-    b->rs_bpr.assign(n, 0u);
-    std::map<uint64_t, std::pair<uint32_t, uint32_t>> seen;  // (in, out) -> offsets of bounds, coefficients
-    const uint32_t filter = b->filter;                       // (one per batch: the keys need not hold it)
-    auto axis = [&](uint32_t in, uint32_t out, uint32_t &bo, uint32_t &ko, uint32_t &ks) {
-        ks = resample_ksize_filtered(filter, in, out);
-        const uint64_t key = ((uint64_t)in << 32) | out;
-        auto it = seen.find(key);
-        if (it != seen.end()) return bo = it->second.first, ko = it->second.second, true;
-        const size_t base = b->rs_tab.size(), end = base + 2u * (size_t)out + (size_t)out * ks;
-        if (end > 0xffffffffull) return false;
-        b->rs_tab.resize(end);
-        bo = (uint32_t)base, ko = (uint32_t)(base + 2u * out);
-        resample_coefficients_filtered(filter, in, out, b->rs_tab.data() + bo, b->rs_tab.data() + ko, ks);
-        seen[key] = {bo, ko};
-        return true;
-    };
-    // a placed batch: entries [first, first + count) of the axis (in, out) — the visible range, nothing else is tabulated
-    std::map<std::array<uint32_t, 4>, std::pair<uint32_t, uint32_t>> seen_range;
-    auto axis_range = [&](uint32_t in, uint32_t out, uint32_t first, uint32_t count, uint32_t &bo, uint32_t &ko, uint32_t &ks) {
-        ks = resample_ksize_filtered(filter, in, out);
-        const std::array<uint32_t, 4> key = {in, out, first, count};
-        auto it = seen_range.find(key);
-        if (it != seen_range.end()) return bo = it->second.first, ko = it->second.second, true;
-        const size_t base = b->rs_tab.size(), end = base + 2u * (size_t)count + (size_t)count * ks;
-        if (end > 0xffffffffull) return false;
-        b->rs_tab.resize(end);
-        bo = (uint32_t)base, ko = (uint32_t)(base + 2u * count);
-        resample_coefficients_range_filtered(filter, in, out, first, count, b->rs_tab.data() + bo, b->rs_tab.data() + ko, ks);
-        seen_range[key] = {bo, ko};
-        return true;
-    };
-    if (b->placed) b->rs_places.assign(n, Place{});
-    size_t k = 0;
-    for (uint32_t i = 0; i < n; i++) {
-        const jpgpu_image_desc &d = b->descs[i];
-        ResampleJob &j = b->rs_jobs[i];
-        window_grid(d.components, d.ncomp, d.out_w, d.out_h, j.in_w, j.in_h);
-        if (k < b->win.ids.size() && b->win.ids[k] == i) j.in_w = b->win.geoms[k].ww, j.in_h = b->win.geoms[k].wh, k++;
-        j.nc = d.ncomp, j.out_w = b->rs_w, j.out_h = b->rs_h;
-        if (b->flags & JPGPU_BATCH_RGB_OUTPUT) j.nc = 3u, j.src_nc = d.ncomp == 3u ? 0u : d.ncomp;  // (gray / CMYK: converted by the horizontal pass)
-        if (b->placed) {  // (the job of the visible rectangle)
-            const jpgpu_placement &pl = b->pl[i];
-            Place &p = b->rs_places[i];
-            uint32_t fx = 0, fy = 0;
-            if (!placed_axis(pl.rw, pl.x, b->rs_w, fx, j.out_w, p.vx) || !placed_axis(pl.rh, pl.y, b->rs_h, fy, j.out_h, p.vy))
-                return set_err(b->err, JPGPU_ERR_FORMAT, "image %u: the placement shows no pixel", i);
-            p.cw = b->rs_w, p.ch = b->rs_h, p.fill = b->pl_fill;
-            if (!axis_range(j.in_w, pl.rw, fx, j.out_w, j.hb, j.hk, j.hks) || !axis_range(j.in_h, pl.rh, fy, j.out_h, j.vb, j.vk, j.vks))
-                return set_err(b->err, JPGPU_ERR_UNSUPPORTED, "image %u: resample tables of the batch exceed 2^32 words", i);
-            continue;
-        }
-        if (!axis(j.in_w, j.out_w, j.hb, j.hk, j.hks) || !axis(j.in_h, j.out_h, j.vb, j.vk, j.vks))
-            return set_err(b->err, JPGPU_ERR_UNSUPPORTED, "image %u: resample tables of the batch exceed 2^32 words", i);
-    }
-    for (uint32_t i = 0; i < n; i++) {  // (the tables stand still now)
-        ResampleJob &j = b->rs_jobs[i];
-        if (b->placed) {
-            if (!placed_plan(j, b->rs_places[i], b->rs_tab.data())) return set_err(b->err, JPGPU_ERR_INTERNAL, "image %u: no resample plan", i);
-            b->rs_max_bands = std::max(b->rs_max_bands, b->rs_places[i].bands);
-        } else {
-            if (!resample_plan(j, b->rs_tab.data())) return set_err(b->err, JPGPU_ERR_INTERNAL, "image %u: no resample plan", i);
-            // (JPGPU_RS_ROLL, read per call: 1 never, 2 / 4 / 8 every candidate with that many bands per run — the benchmark's A/B)
-            const char *knob = getenv("JPGPU_RS_ROLL");
-            const uint32_t bpr = b->rs_bpr[i] = resample_roll_bpr(j, b->rs_tab.data(), filter, knob ? (uint32_t)atoi(knob) : 0u);
-            if (bpr) b->rs_max_runs = std::max(b->rs_max_runs, (j.bands + bpr - 1u) / bpr);
-            else b->rs_max_bands = std::max(b->rs_max_bands, j.bands);
-        }
-        b->rs_lds_bytes = std::max(b->rs_lds_bytes, j.lds_bytes);
-    }
-    const size_t roll_at = b->path.find("+roll");  // (the path names the route where any image took it; other windows may change that)
-    if (roll_at != std::string::npos) b->path.erase(roll_at, 5);
-    if (b->rs_max_runs) b->path.insert(std::min(b->path.find("+warp"), b->path.size()), "+roll");  // (the last word of the u8 batch's path: in front of a warp's)
-    B_HIP(batch_wait_enqueued(b));  // (a decode still queued reads the tables)
-    if (b->rs_tab.size() > b->rs_tab_cap) {
-        B_HIP(hipDeviceSynchronize());
-        B_HIP(grow_device(b->d_rs_tab, b->rs_tab_cap, b->rs_tab.size()));
-    }
-    B_HIP(hipMemcpy(b->d_rs_tab, b->rs_tab.data(), b->rs_tab.size() * sizeof(int32_t), hipMemcpyHostToDevice));
-    if (b->d_rs_bpr) B_HIP(hipMemcpy(b->d_rs_bpr, b->rs_bpr.data(), (size_t)n * sizeof(uint32_t), hipMemcpyHostToDevice));
-    b->jobs_dirty = true;  // (the jobs go up with the others)
-    return JPGPU_OK;
-}
 
 // every image's quantization tables to the device (unused slots: ones)
 static int batch_upload_qt(jpgpu_batch *b) {
@@ -113,82 +20,12 @@ static int batch_upload_qt(jpgpu_batch *b) {
     return JPGPU_OK;
 }
 
-// The TensorJobs of a tensor batch: every image's resample job, its plane pitch and its flip.  They travel on the decode's stream from a
-// pinned mirror (fresh flips come with every call of a loader: a blocking copy per sub-batch would hold the uploader thread up).
-static int batch_upload_tensor_jobs(jpgpu_batch *b, hipStream_t stream) {
-    const uint32_t n = (uint32_t)b->descs.size();
-    if (!b->h_tn_jobs && !b->h_ptn_jobs) {
-        if (b->placed) B_HIP(hipHostMalloc((void **)&b->h_ptn_jobs, (size_t)n * sizeof(PlacedTensorJob), hipHostMallocDefault));
-        else B_HIP(hipHostMalloc((void **)&b->h_tn_jobs, (size_t)n * 2u * sizeof(TensorJob), hipHostMallocDefault));
-        B_HIP(hipEventCreateWithFlags(&b->tn_sent, hipEventDisableTiming));
-    } else {
-        B_HIP(hipEventSynchronize(b->tn_sent));  // (the copy before this one has read the mirror)
-    }
-    if (b->placed) {  // (the same records with every image's placement behind them)
-        for (uint32_t i = 0; i < n; i++) {
-            b->h_ptn_jobs[i].t.r = b->rs_jobs[i];
-            b->h_ptn_jobs[i].t.plane = b->rs_w * b->rs_h;
-            b->h_ptn_jobs[i].t.flip = b->tn_flips[i] ? 1u : 0u;
-            b->h_ptn_jobs[i].p = b->rs_places[i];
-        }
-        B_HIP(hipMemcpyAsync(b->d_ptn_jobs, b->h_ptn_jobs, (size_t)n * sizeof(PlacedTensorJob), hipMemcpyHostToDevice, stream));
-        B_HIP(hipEventRecord(b->tn_sent, stream));
-        b->tn_dirty = false;
-        return JPGPU_OK;
-    }
-    for (uint32_t i = 0; i < n; i++) {
-        b->h_tn_jobs[i].r = b->rs_jobs[i];
-        b->h_tn_jobs[i].plane = b->rs_w * b->rs_h;
-        b->h_tn_jobs[i].flip = b->tn_flips[i] ? 1u : 0u;
-        if (!b->rs_max_runs) continue;
-        b->h_tn_jobs[n + i] = b->h_tn_jobs[i];               // (the run launch's: the real job)
-        if (b->rs_bpr[i]) b->h_tn_jobs[i].r.bands = 0u;  // (the band launch's: no band of this image)
-    }
-    B_HIP(hipMemcpyAsync(b->d_tn_jobs, b->h_tn_jobs, (size_t)n * (b->rs_max_runs ? 2u : 1u) * sizeof(TensorJob), hipMemcpyHostToDevice, stream));
-    B_HIP(hipEventRecord(b->tn_sent, stream));
-    b->tn_dirty = false;
-    return JPGPU_OK;
-}
-
-// The WarpJobs of a warped batch and the N-sep tables behind them: every image's matrix, its flip, where it reads and writes.  From a
-// pinned mirror on the decode's stream, as the TensorJobs: a decode queued earlier keeps the matrices it was enqueued with.
-static size_t warp_jobs_bytes(const jpgpu_batch *b) { return b->descs.size() * (sizeof(WarpJob) + ((size_t)b->rs_w + b->rs_h) * sizeof(int32_t)); }
-static int batch_upload_warp_jobs(jpgpu_batch *b, hipStream_t stream) {
-    const uint32_t n = (uint32_t)b->descs.size();
-    if (!b->h_wp_jobs) {
-        B_HIP(hipHostMalloc((void **)&b->h_wp_jobs, warp_jobs_bytes(b), hipHostMallocDefault));
-        B_HIP(hipEventCreateWithFlags(&b->wp_sent, hipEventDisableTiming));
-    } else {
-        B_HIP(hipEventSynchronize(b->wp_sent));  // (the copy before this one has read the mirror)
-    }
-    WarpJob *jobs = reinterpret_cast<WarpJob *>(b->h_wp_jobs);
-    int32_t *tabs = reinterpret_cast<int32_t *>(b->h_wp_jobs + (size_t)n * sizeof(WarpJob));
-    const bool rgb = (b->flags & JPGPU_BATCH_RGB_OUTPUT) != 0;
-    for (uint32_t i = 0; i < n; i++) {
-        WarpJob &j = jobs[i];
-        j.src = b->d_wsrc + b->wsrc_off[i], j.dst = b->d_out + b->out_off[i];
-        j.w = b->rs_w, j.h = b->rs_h, j.nc = rgb ? 3u : b->descs[i].ncomp;
-        j.flip = (b->tn_es && b->tn_flips[i]) ? 1u : 0u;
-        j.fill = b->wp_fill, j.plane = b->rs_w * b->rs_h;
-        j.tab = i * (b->rs_w + b->rs_h);
-        warp_job_matrix(j, b->wp_m[i].m, b->wp_filter, tabs + j.tab);
-    }
-    B_HIP(hipMemcpyAsync(b->d_wp_jobs, b->h_wp_jobs, warp_jobs_bytes(b), hipMemcpyHostToDevice, stream));
-    B_HIP(hipEventRecord(b->wp_sent, stream));
-    b->wp_dirty = false;
-    return JPGPU_OK;
-}
-
 static int batch_refresh_jobs(jpgpu_batch *b, hipStream_t stream = nullptr) {
     // host-side classes are part of the launch tables (one launch per class: fused_bind); with device-side classes they
     // travel in a small table of their own, asynchronously, and the launch tables stay as they are
     const bool need_bind = b->jobs_dirty || (b->cls_dirty && !b->dev_classes);
-    if (!need_bind && b->tn_dirty && b->d_coef && b->d_out) {  // (other flips alone: the TensorJobs, nothing else)
-        int rc = batch_upload_tensor_jobs(b, stream);
-        if (rc) return rc;
-    }
-    if (!need_bind && b->wp_dirty && b->d_coef && b->d_out) {  // (other matrices or flips alone: the WarpJobs, nothing else)
-        int rc = batch_upload_warp_jobs(b, stream);
+    if (!need_bind && b->d_coef && b->d_out) {  // (other flips or matrices alone: the records that hold them, nothing else)
+        int rc = output_bind(b, stream, false);
         if (rc) return rc;
     }
     if (!need_bind && !b->cls_dirty) return JPGPU_OK;
@@ -209,7 +46,6 @@ static int batch_refresh_jobs(jpgpu_batch *b, hipStream_t stream = nullptr) {
     }
     b->cls_dirty = false;
     if (!need_bind) return JPGPU_OK;
-    const uint32_t n = (uint32_t)b->descs.size();
     b->plane_jobs.clear();
     b->image_jobs.clear();
     for (uint32_t i : b->generic_ids) {
@@ -246,29 +82,8 @@ static int batch_refresh_jobs(jpgpu_batch *b, hipStream_t stream = nullptr) {
         rc = fused_bind(fp, b->d_coef, pix, b->d_qt, b->coef_off, pix_off, b->sane, b->err);
         if (rc) return rc;
     }
-    if (b->rs_w) {
-        for (uint32_t i = 0; i < n; i++) b->rs_jobs[i].src = pix + pix_off[i], b->rs_jobs[i].dst = b->warp ? b->d_wsrc + b->wsrc_off[i] : b->d_out + b->out_off[i];
-        if (b->warp) {  // (the u8 resample of the same arguments writes the warp's source; the warp writes the output)
-            rc = batch_upload_warp_jobs(b, stream);
-            if (rc) return rc;
-        }
-        if (b->tn_es && !b->warp) {
-            rc = batch_upload_tensor_jobs(b, stream);
-            if (rc) return rc;
-        } else if (b->placed) {
-            std::vector<PlacedJob> pj(n);
-            for (uint32_t i = 0; i < n; i++) pj[i].r = b->rs_jobs[i], pj[i].p = b->rs_places[i];
-            B_HIP(hipMemcpy(b->d_pl_jobs, pj.data(), (size_t)n * sizeof(PlacedJob), hipMemcpyHostToDevice));
-        } else if (b->rs_max_runs) {  // (band launch: images in runs have no band; run launch: the real jobs)
-            std::vector<ResampleJob> both(b->rs_jobs);
-            both.insert(both.end(), b->rs_jobs.begin(), b->rs_jobs.end());
-            for (uint32_t i = 0; i < n; i++)
-                if (b->rs_bpr[i]) both[i].bands = 0u;
-            B_HIP(hipMemcpy(b->d_rs_jobs, both.data(), (size_t)n * 2u * sizeof(ResampleJob), hipMemcpyHostToDevice));
-        } else {
-            B_HIP(hipMemcpy(b->d_rs_jobs, b->rs_jobs.data(), (size_t)n * sizeof(ResampleJob), hipMemcpyHostToDevice));
-        }
-    }
+    rc = output_bind(b, stream, true);
+    if (rc) return rc;
     if (b->qt_dirty) {
         rc = batch_upload_qt(b);
         if (rc) return rc;
@@ -280,11 +95,9 @@ static int batch_refresh_jobs(jpgpu_batch *b, hipStream_t stream = nullptr) {
 
 extern "C" {
 
-// rs_w, rs_h: the output size of jpgpu_batch_create_resized (0, 0: none); tensor: the format of jpgpu_batch_create_tensor (NULL: none)
-// placements, fill: those of jpgpu_batch_create_placed (NULL: none)
-static int batch_create(int device, const jpgpu_image_desc *descs, const jpgpu_window *windows, uint32_t rs_w, uint32_t rs_h,
-                        const jpgpu_tensor_format *tensor, uint32_t n_images, uint32_t flags, jpgpu_batch **out,
-                        const jpgpu_placement *placements = nullptr, const uint8_t *fill = nullptr, const jpgpu_warp_options *warp = nullptr) {
+// placements: those of jpgpu_batch_create_placed (NULL, or without an output size: none); spec: everything else of the fixed-output stage
+static int batch_create(int device, const jpgpu_image_desc *descs, const jpgpu_window *windows, const jpgpu_placement *placements, uint32_t n_images,
+                        uint32_t flags, const OutputSpec &spec, jpgpu_batch **out) {
     if (!out) return JPGPU_ERR_FORMAT;
     *out = nullptr;
     if (!descs || n_images == 0 || n_images > 65535) return JPGPU_ERR_FORMAT;
@@ -292,47 +105,20 @@ static int batch_create(int device, const jpgpu_image_desc *descs, const jpgpu_w
     *out = b;  // returned even on failure so the caller can read last_error, then destroy
     b->device = device;
     b->flags = flags;
-    const bool resized = rs_w != 0 || rs_h != 0;
-    if (resized && (rs_w == 0 || rs_h == 0 || rs_w > RS_MAX_OUT || rs_h > RS_MAX_OUT))
-        return set_err(b->err, JPGPU_ERR_FORMAT, "output size %ux%u: width and height must be 1..%u", rs_w, rs_h, RS_MAX_OUT);
-    const uint32_t filter = (flags >> 8) & 15u;  // JPGPU_BATCH_FILTER(f): 0 is BILINEAR, so flags without the bits mean what they meant
-    if (filter >= RS_FILTERS) return set_err(b->err, JPGPU_ERR_FORMAT, "resample filter %u: the ids are 0..%u (JPGPU_FILTER_*)", filter, RS_FILTERS - 1u);
-    if (filter && !resized)
-        return set_err(b->err, JPGPU_ERR_UNSUPPORTED, "a resample filter (%s) needs an output size (jpgpu_batch_create_resized / _create_tensor / _create_placed)",
-                       resample_filter_name(filter));
-    b->filter = filter;
-    const bool rgb = (flags & JPGPU_BATCH_RGB_OUTPUT) != 0;  // (every image gives three channels: the resample converts gray and CMYK)
-    if (rgb && !resized)
-        return set_err(b->err, JPGPU_ERR_UNSUPPORTED, "JPGPU_BATCH_RGB_OUTPUT needs an output size (jpgpu_batch_create_resized / _create_tensor)");
-    if (warp) {  // (every image starts with the identity)
-        if (!resized) return set_err(b->err, JPGPU_ERR_FORMAT, "a warp needs an output size");
-        if (warp->filter > WP_BILINEAR || warp->reserved != 0)
-            return set_err(b->err, JPGPU_ERR_FORMAT, "warp options: filter %u, reserved %u (JPGPU_WARP_NEAREST or JPGPU_WARP_BILINEAR, reserved 0)", warp->filter, warp->reserved);
-        b->warp = true, b->wp_filter = warp->filter;
-        b->wp_fill = (uint32_t)warp->fill[0] | ((uint32_t)warp->fill[1] << 8) | ((uint32_t)warp->fill[2] << 16) | ((uint32_t)warp->fill[3] << 24);
-        b->wp_m.assign(n_images, jpgpu_warp{{1.0, 0.0, 0.0, 0.0, 1.0, 0.0}});
-    }
-    if (tensor) {  // (the format against the channels of every image of the call, before anything is allocated)
-        if (!resized) return set_err(b->err, JPGPU_ERR_FORMAT, "a tensor format needs an output size");
-        uint32_t nc_max = rgb ? 3u : 1u;
-        for (uint32_t i = 0; i < n_images && !rgb; i++) nc_max = std::max(nc_max, std::min<uint32_t>(descs[i].ncomp, 4u));
-        const char *why = nullptr;
-        if (!tensor_format_ok(tensor->dtype, tensor->reserved, tensor->mean, tensor->std, nc_max, why)) return set_err(b->err, JPGPU_ERR_FORMAT, "tensor format: %s", why);
-    }
+    b->o.spec = spec;
+    const bool resized = spec.sized();
+    std::string why;
+    int rc = output_rule(spec, why);
+    if (rc) return set_err(b->err, rc, "%s", why.c_str());
+    for (uint32_t i = 0; i < n_images; i++)  // (the format against the channels of every image of the call, before a device is touched)
+        if (output_tensor_rule(spec, std::min<uint32_t>(std::max<uint32_t>(descs[i].ncomp, 1u), 4u), why)) return set_err(b->err, JPGPU_ERR_FORMAT, "image %u: %s", i, why.c_str());
     if (placements && resized) {  // (every placement shows a pixel; one that differs from the whole output makes the batch a placed one)
-        b->pl.assign(placements, placements + n_images);
-        for (uint32_t i = 0; i < n_images; i++) {
-            jpgpu_placement &pl = b->pl[i];
-            if (pl.rw == 0 || pl.rh == 0) pl = jpgpu_placement{(uint16_t)rs_w, (uint16_t)rs_h, 0, 0};
-            uint32_t first, count, v0;
-            if (!placed_axis(pl.rw, pl.x, rs_w, first, count, v0) || !placed_axis(pl.rh, pl.y, rs_h, first, count, v0))
-                return set_err(b->err, JPGPU_ERR_FORMAT, "image %u: the placement %ux%u at (%d, %d) shows no pixel of the %ux%u output", i, pl.rw, pl.rh, pl.x, pl.y,
-                               rs_w, rs_h);
-            if (pl.rw != rs_w || pl.rh != rs_h || pl.x != 0 || pl.y != 0) b->placed = true;
-        }
-        if (fill) b->pl_fill = (uint32_t)fill[0] | ((uint32_t)fill[1] << 8) | ((uint32_t)fill[2] << 16) | ((uint32_t)fill[3] << 24);
+        const uint32_t i = normalise_placements(placements, n_images, spec.w, spec.h, b->o.pl, b->o.placed);
+        if (i < n_images)
+            return set_err(b->err, JPGPU_ERR_FORMAT, "image %u: the placement %ux%u at (%d, %d) shows no pixel of the %ux%u output", i, b->o.pl[i].rw, b->o.pl[i].rh,
+                           b->o.pl[i].x, b->o.pl[i].y, spec.w, spec.h);
     }
-    int rc = use_device(device, b->err);
+    rc = use_device(device, b->err);
     if (rc) return rc;
     b->descs.assign(descs, descs + n_images);
     b->coef_off.assign((size_t)n_images * 4, 0);
@@ -358,15 +144,13 @@ static int batch_create(int device, const jpgpu_image_desc *descs, const jpgpu_w
         rc = build_image_job(d.components, d.ncomp, dummy, d.out_w, d.out_h, d.color_transform, nullptr, ij, out_len, b->err);
         if (rc) return rc;
         b->out_full_len[i] = out_len;
-        if (resized && ij.color_fn == CC_NONE && d.ncomp > 1)
-            return set_err(b->err, JPGPU_ERR_UNSUPPORTED, "image %u: no output size for planar output (ColorTransform None with %u components)", i, d.ncomp);
-        if (rgb && d.ncomp != 1 && d.ncomp != 3 && d.ncomp != 4) return set_err(b->err, JPGPU_ERR_UNSUPPORTED, "image %u: no RGB output for %u components", i, d.ncomp);
+        rc = output_image_rule(spec, d.ncomp, ij.color_fn, why);
+        if (rc) return set_err(b->err, rc, "image %u: %s", i, why.c_str());
         // a window smaller than the image: the window group (an empty window or one that covers the image is no window)
         bool windowed = false;
         if (windows) {
             uint32_t gw = 0, gh = 0;
             WindowGeom wg;
-            std::string why;
             rc = window_rule(d, windows[i], windowed, gw, gh, wg, why);
             if (rc) return set_err(b->err, rc, "image %u: %s", i, why.c_str());
             if (windowed) {
@@ -409,20 +193,6 @@ static int batch_create(int device, const jpgpu_image_desc *descs, const jpgpu_w
     b->coef_bytes = std::max<size_t>(co, 256);
     b->out_bytes = arena_layout(lens, b->out_off, b->out_len);
     b->plane_bytes_total = std::max<size_t>(po, 256);
-    if (resized) {  // what was laid out so far is the intermediate arena; the output arena holds rs_h x rs_w x ncomp bytes per image
-        b->rs_w = rs_w, b->rs_h = rs_h;
-        b->pix_off = b->out_off, b->pix_len = b->out_len, b->pix_bytes = b->out_bytes;
-        if (tensor) b->tn_es = tensor_elem_bytes(tensor->dtype), b->tn_flips.assign(n_images, 0);
-        for (uint32_t i = 0; i < n_images; i++) lens[i] = (size_t)rs_w * rs_h * (rgb ? 3u : b->descs[i].ncomp) * (tensor ? b->tn_es : 1u);
-        b->out_bytes = arena_layout(lens, b->out_off, b->out_len);
-    }
-    std::vector<size_t> wsrc_len;
-    size_t wsrc_bytes = 0;
-    if (b->warp) {  // (what the u8 batch's output arena would be)
-        for (uint32_t i = 0; i < n_images; i++) lens[i] = (size_t)rs_w * rs_h * (rgb ? 3u : b->descs[i].ncomp);
-        wsrc_bytes = arena_layout(lens, b->wsrc_off, wsrc_len);
-    }
-
     {
         std::vector<uint32_t> keys;
         for (uint32_t i = 0; i < n_images; i++)
@@ -447,12 +217,14 @@ static int batch_create(int device, const jpgpu_image_desc *descs, const jpgpu_w
     if (!b->scaled.empty()) b->path = (b->fused.empty() && b->generic_ids.empty()) ? b->scaled_name : "mixed";
     if (!b->win.empty()) b->path = b->path.empty() ? "window" : "mixed";
     if (b->path.empty()) b->path = "generic";
-    if (rgb) b->path += "+rgb";
-    if (b->placed) b->path += "+place";
+    if (spec.rgb) b->path += "+rgb";
+    if (b->o.placed) b->path += "+place";
     if (resized) b->path += "+resize";
-    if (filter) b->path += std::string(":") + resample_filter_name(filter);
-    if (b->warp) b->path += b->wp_filter == WP_BILINEAR ? "+warp:bilinear" : "+warp";
-    if (tensor) b->path += "+tensor";
+    if (spec.filter) b->path += std::string(":") + resample_filter_name(spec.filter);
+    if (spec.warp) b->path += spec.wp.filter == WP_BILINEAR ? "+warp:bilinear" : "+warp";
+    if (spec.tensor) b->path += "+tensor";
+    rc = output_create(b);  // (what was laid out so far becomes the intermediate arena)
+    if (rc) return rc;
     const size_t full = arena_layout(b->out_full_len);  // (what the whole images take)
     if (!(flags & JPGPU_BATCH_EXTERNAL_BUFFERS)) {
         B_HIP(hipMalloc((void **)&b->d_coef, b->coef_bytes));
@@ -461,34 +233,6 @@ static int batch_create(int device, const jpgpu_image_desc *descs, const jpgpu_w
         b->out_cap = (b->win.empty() || resized) ? b->out_bytes : arena_headroom(b->out_bytes, full);
         B_HIP(hipMalloc((void **)&b->d_out, b->out_cap));
         b->own_out = true;
-    }
-    if (resized) {  // (the same headroom for other windows, in the intermediate arena)
-        b->pix_cap = b->win.empty() ? b->pix_bytes : arena_headroom(b->pix_bytes, full);
-        B_HIP(hipMalloc((void **)&b->d_pix, b->pix_cap));
-        if (b->warp) {
-            B_HIP(hipMalloc((void **)&b->d_wsrc, wsrc_bytes));
-            B_HIP(hipMalloc((void **)&b->d_wp_jobs, warp_jobs_bytes(b)));
-            b->wp_dirty = true;
-        }
-        const bool rs_tensor = tensor && !b->warp;  // (a warp: the resample's jobs are the u8 ones, the warp writes the tensor)
-        if (tensor) {  // (the table of four channels: every image looks up its own first ncomp rows)
-            B_HIP(hipMalloc(&b->d_tn_table, TN_TABLE_MAX));
-            std::vector<uint32_t> table(TN_TABLE_MAX / 4u, 0u);
-            uint32_t nc_max = rgb ? 3u : 1u;
-            for (uint32_t i = 0; i < n_images && !rgb; i++) nc_max = std::max<uint32_t>(nc_max, b->descs[i].ncomp);
-            tensor_table(tensor->dtype, tensor->mean, tensor->std, nc_max, table.data());
-            B_HIP(hipMemcpy(b->d_tn_table, table.data(), TN_TABLE_MAX, hipMemcpyHostToDevice));
-        }
-        if (rs_tensor && b->placed) {
-            B_HIP(hipMalloc((void **)&b->d_ptn_jobs, (size_t)n_images * sizeof(PlacedTensorJob)));
-        } else if (rs_tensor) {
-            B_HIP(hipMalloc((void **)&b->d_tn_jobs, (size_t)n_images * 2u * sizeof(TensorJob)));
-        } else if (b->placed) {
-            B_HIP(hipMalloc((void **)&b->d_pl_jobs, (size_t)n_images * sizeof(PlacedJob)));
-        } else {
-            B_HIP(hipMalloc((void **)&b->d_rs_jobs, (size_t)n_images * 2u * sizeof(ResampleJob)));
-        }
-        if (!b->placed) B_HIP(hipMalloc((void **)&b->d_rs_bpr, (size_t)n_images * sizeof(uint32_t)));
     }
     if (!b->generic_ids.empty()) B_HIP(hipMalloc((void **)&b->d_planes, b->plane_bytes_total));
     for (FusedPlan &fp : b->fused) {
@@ -509,89 +253,55 @@ static int batch_create(int device, const jpgpu_image_desc *descs, const jpgpu_w
     B_HIP(hipEventCreate(&b->ev0));
     B_HIP(hipEventCreate(&b->ev1));
     B_HIP(hipEventCreateWithFlags(&b->enqueued, hipEventDisableTiming));
-    if (resized) return batch_resample_tables(b);
-    return JPGPU_OK;
+    return resized ? output_retable(b) : JPGPU_OK;
 }
 
+// The spec of a public creator: the size, the RGB and filter bits of its flags, and the options it has (NULL: none).
+static OutputSpec spec_of(uint32_t flags, uint32_t w = 0, uint32_t h = 0, const jpgpu_tensor_format *tensor = nullptr, const uint8_t *fill = nullptr,
+                          const jpgpu_warp_options *warp = nullptr) {
+    OutputSpec s;
+    s.w = w, s.h = h, s.rgb = (flags & JPGPU_BATCH_RGB_OUTPUT) != 0;
+    s.filter = (flags >> 8) & 15u;  // JPGPU_BATCH_FILTER(f): 0 is BILINEAR, so flags without the bits mean what they meant
+    if (tensor) s.tensor = true, s.tn = *tensor;
+    if (fill) memcpy(s.fill, fill, 4);
+    if (warp) s.warp = true, s.wp = *warp;
+    return s;
+}
+// A creator with an output size was given none (0 x 0 would mean "none" to batch_create): a batch that holds the creator's own message.
+static int refuse_no_size(jpgpu_batch **out, const char *message, uint32_t w, uint32_t h) {
+    if (!out) return JPGPU_ERR_FORMAT;
+    *out = new jpgpu_batch();
+    return set_err((*out)->err, JPGPU_ERR_FORMAT, message, w, h, RS_MAX_OUT);
+}
+static const char kNoSize[] = "output size %ux%u: width and height must be 1..%u";
+
 int jpgpu_batch_create(int device, const jpgpu_image_desc *descs, uint32_t n_images, uint32_t flags, jpgpu_batch **out) {
-    return batch_create(device, descs, nullptr, 0, 0, nullptr, n_images, flags, out);
+    return batch_create(device, descs, nullptr, nullptr, n_images, flags, spec_of(flags), out);
 }
-int jpgpu_batch_create_windowed(int device, const jpgpu_image_desc *descs, const jpgpu_window *windows, uint32_t n_images, uint32_t flags,
-                                jpgpu_batch **out) {
-    return batch_create(device, descs, windows, 0, 0, nullptr, n_images, flags, out);
+int jpgpu_batch_create_windowed(int device, const jpgpu_image_desc *descs, const jpgpu_window *windows, uint32_t n_images, uint32_t flags, jpgpu_batch **out) {
+    return batch_create(device, descs, windows, nullptr, n_images, flags, spec_of(flags), out);
 }
-int jpgpu_batch_create_resized(int device, const jpgpu_image_desc *descs, const jpgpu_window *windows, uint16_t out_w, uint16_t out_h,
-                               uint32_t n_images, uint32_t flags, jpgpu_batch **out) {
-    if (out_w == 0 || out_h == 0) {  // (0, 0 would mean "none" below: refuse it here)
-        if (!out) return JPGPU_ERR_FORMAT;
-        jpgpu_batch *b = new jpgpu_batch();
-        *out = b;
-        return set_err(b->err, JPGPU_ERR_FORMAT, "output size %ux%u: width and height must be 1..%u", out_w, out_h, RS_MAX_OUT);
-    }
-    return batch_create(device, descs, windows, out_w, out_h, nullptr, n_images, flags, out);
+int jpgpu_batch_create_resized(int device, const jpgpu_image_desc *descs, const jpgpu_window *windows, uint16_t out_w, uint16_t out_h, uint32_t n_images, uint32_t flags,
+                               jpgpu_batch **out) {
+    if (out_w == 0 || out_h == 0) return refuse_no_size(out, kNoSize, out_w, out_h);
+    return batch_create(device, descs, windows, nullptr, n_images, flags, spec_of(flags, out_w, out_h), out);
 }
 int jpgpu_batch_create_tensor(int device, const jpgpu_image_desc *descs, const jpgpu_window *windows, uint16_t out_w, uint16_t out_h,
                               const jpgpu_tensor_format *format, uint32_t n_images, uint32_t flags, jpgpu_batch **out) {
-    if (out_w == 0 || out_h == 0 || !format) {  // (no output size, no format: refused here — below they would mean "none")
-        if (!out) return JPGPU_ERR_FORMAT;
-        jpgpu_batch *b = new jpgpu_batch();
-        *out = b;
-        if (!format) return set_err(b->err, JPGPU_ERR_FORMAT, "jpgpu_batch_create_tensor: no tensor format");
-        return set_err(b->err, JPGPU_ERR_FORMAT, "a tensor format needs an output size (%ux%u: width and height must be 1..%u)", out_w, out_h, RS_MAX_OUT);
-    }
-    return batch_create(device, descs, windows, out_w, out_h, format, n_images, flags, out);
+    if (out_w == 0 || out_h == 0 || !format)  // (no output size, no format: below they would mean "none")
+        return refuse_no_size(out, format ? "a tensor format needs an output size (%ux%u: width and height must be 1..%u)" : "jpgpu_batch_create_tensor: no tensor format", out_w, out_h);
+    return batch_create(device, descs, windows, nullptr, n_images, flags, spec_of(flags, out_w, out_h, format), out);
 }
-int jpgpu_batch_create_placed(int device, const jpgpu_image_desc *descs, const jpgpu_window *windows, const jpgpu_placement *placements,
-                              const uint8_t *fill, uint16_t out_w, uint16_t out_h, const jpgpu_tensor_format *format, uint32_t n_images,
-                              uint32_t flags, jpgpu_batch **out) {
-    if (out_w == 0 || out_h == 0) {  // (0, 0 would mean "none" below: refuse it here)
-        if (!out) return JPGPU_ERR_FORMAT;
-        jpgpu_batch *b = new jpgpu_batch();
-        *out = b;
-        return set_err(b->err, JPGPU_ERR_FORMAT, "output size %ux%u: width and height must be 1..%u", out_w, out_h, RS_MAX_OUT);
-    }
-    return batch_create(device, descs, windows, out_w, out_h, format, n_images, flags, out, placements, fill);
+int jpgpu_batch_create_placed(int device, const jpgpu_image_desc *descs, const jpgpu_window *windows, const jpgpu_placement *placements, const uint8_t *fill,
+                              uint16_t out_w, uint16_t out_h, const jpgpu_tensor_format *format, uint32_t n_images, uint32_t flags, jpgpu_batch **out) {
+    return jpgpu_batch_create_warped(device, descs, windows, placements, fill, out_w, out_h, format, nullptr, n_images, flags, out);
 }
-int jpgpu_batch_set_flips(jpgpu_batch *b, const uint8_t *flips) {
-    if (!b) return JPGPU_ERR_FORMAT;
-    if (!b->tn_es) return set_err(b->err, JPGPU_ERR_UNSUPPORTED, "jpgpu_batch_set_flips: the batch has no tensor format");
-    for (size_t i = 0; i < b->tn_flips.size(); i++) b->tn_flips[i] = flips && flips[i] ? 1 : 0;
-    if (b->warp) b->wp_dirty = true;  // (a warped batch: the flip is a field of the WarpJobs)
-    else b->tn_dirty = true;
-    return JPGPU_OK;
+int jpgpu_batch_create_warped(int device, const jpgpu_image_desc *descs, const jpgpu_window *windows, const jpgpu_placement *placements, const uint8_t *fill,
+                              uint16_t out_w, uint16_t out_h, const jpgpu_tensor_format *format, const jpgpu_warp_options *warp, uint32_t n_images, uint32_t flags,
+                              jpgpu_batch **out) {
+    if (out_w == 0 || out_h == 0) return refuse_no_size(out, warp ? "a warp needs an output size (%ux%u: width and height must be 1..%u)" : kNoSize, out_w, out_h);
+    return batch_create(device, descs, windows, placements, n_images, flags, spec_of(flags, out_w, out_h, format, fill, warp), out);
 }
-int jpgpu_batch_create_warped(int device, const jpgpu_image_desc *descs, const jpgpu_window *windows, const jpgpu_placement *placements,
-                              const uint8_t *fill, uint16_t out_w, uint16_t out_h, const jpgpu_tensor_format *format, const jpgpu_warp_options *warp,
-                              uint32_t n_images, uint32_t flags, jpgpu_batch **out) {
-    if (!warp) return jpgpu_batch_create_placed(device, descs, windows, placements, fill, out_w, out_h, format, n_images, flags, out);
-    if (out_w == 0 || out_h == 0) {  // (0, 0 would mean "none" below: refuse it here)
-        if (!out) return JPGPU_ERR_FORMAT;
-        jpgpu_batch *b = new jpgpu_batch();
-        *out = b;
-        return set_err(b->err, JPGPU_ERR_FORMAT, "a warp needs an output size (%ux%u: width and height must be 1..%u)", out_w, out_h, RS_MAX_OUT);
-    }
-    return batch_create(device, descs, windows, out_w, out_h, format, n_images, flags, out, placements, fill, warp);
-}
-int jpgpu_batch_set_warps(jpgpu_batch *b, const jpgpu_warp *warps) {
-    if (!b) return JPGPU_ERR_FORMAT;
-    if (!b->warp) return set_err(b->err, JPGPU_ERR_UNSUPPORTED, "jpgpu_batch_set_warps: the batch has no warp (jpgpu_batch_create_warped)");
-    for (size_t i = 0; warps && i < b->wp_m.size(); i++)  // (one refused matrix refuses the call: nothing is changed)
-        if (!warp_check(warps[i].m, b->rs_w, b->rs_h))
-            return set_err(b->err, JPGPU_ERR_FORMAT, "jpgpu_batch_set_warps: image %zu: matrix (%g, %g, %g, %g, %g, %g) refused for %ux%u (jpgpu_warp_check)", i,
-                           warps[i].m[0], warps[i].m[1], warps[i].m[2], warps[i].m[3], warps[i].m[4], warps[i].m[5], b->rs_w, b->rs_h);
-    for (size_t i = 0; i < b->wp_m.size(); i++) b->wp_m[i] = warps ? warps[i] : jpgpu_warp{{1.0, 0.0, 0.0, 0.0, 1.0, 0.0}};
-    b->wp_dirty = true;
-    return JPGPU_OK;
-}
-int jpgpu_warp_check(const jpgpu_warp *warp, uint32_t out_w, uint32_t out_h) {
-    return (warp && out_w && out_h && warp_check(warp->m, out_w, out_h)) ? JPGPU_OK : JPGPU_ERR_FORMAT;
-}
-int jpgpu_warp_nearest_axis(double a, double b, uint32_t out_size, int32_t *idx) {
-    if (!idx && out_size) return JPGPU_ERR_FORMAT;
-    warp_nearest_axis(a, b, out_size, idx);
-    return JPGPU_OK;
-}
-
 void jpgpu_batch_destroy(jpgpu_batch *b) {
     if (!b) return;
     std::string err;
@@ -599,51 +309,21 @@ void jpgpu_batch_destroy(jpgpu_batch *b) {
         hipDeviceSynchronize();
         if (b->own_coef && b->d_coef) hipFree(b->d_coef);
         if (b->own_out && b->d_out) hipFree(b->d_out);
-        if (b->d_planes) hipFree(b->d_planes);
-        if (b->d_pix) hipFree(b->d_pix);
-        if (b->d_rs_jobs) hipFree(b->d_rs_jobs);
-        if (b->d_rs_bpr) hipFree(b->d_rs_bpr);
-        if (b->d_tn_jobs) hipFree(b->d_tn_jobs);
-        if (b->d_pl_jobs) hipFree(b->d_pl_jobs);
-        if (b->d_ptn_jobs) hipFree(b->d_ptn_jobs);
-        if (b->h_ptn_jobs) hipHostFree(b->h_ptn_jobs);
-        if (b->d_wsrc) hipFree(b->d_wsrc);
-        if (b->d_wp_jobs) hipFree(b->d_wp_jobs);
-        if (b->h_wp_jobs) hipHostFree(b->h_wp_jobs);
-        if (b->wp_sent) hipEventDestroy(b->wp_sent);
-        if (b->d_tn_table) hipFree(b->d_tn_table);
-        if (b->h_tn_jobs) hipHostFree(b->h_tn_jobs);
-        if (b->tn_sent) hipEventDestroy(b->tn_sent);
-        if (b->d_rs_tab) hipFree(b->d_rs_tab);
-        if (b->d_qt) hipFree(b->d_qt);
-        if (b->d_compact) hipFree(b->d_compact);
-        if (b->d_expand_jobs) hipFree(b->d_expand_jobs);
-        if (b->h_expand_jobs) hipHostFree(b->h_expand_jobs);
-        if (b->expand_sent) hipEventDestroy(b->expand_sent);
-        if (b->d_entropy) hipFree(b->d_entropy);
-        if (b->h_entropy) hipHostFree(b->h_entropy);
-        if (b->h_entropy_out) hipHostFree(b->h_entropy_out);
-        if (b->entropy_uploaded) hipEventDestroy(b->entropy_uploaded);
-        if (b->entropy_filled) hipEventDestroy(b->entropy_filled);
-        if (b->h_bounce) hipHostFree(b->h_bounce);
-        if (b->d_scan) hipFree(b->d_scan);
-        if (b->h_scan) hipHostFree(b->h_scan);
-        if (b->d_stats) hipFree(b->d_stats);
-        if (b->d_host_cls) hipFree(b->d_host_cls);
-        if (b->h_host_cls) hipHostFree(b->h_host_cls);
-        if (b->d_plane_job_slot) hipFree(b->d_plane_job_slot);
+        for (void *d : {(void *)b->d_planes, (void *)b->d_qt, (void *)b->d_compact, (void *)b->d_expand_jobs, (void *)b->d_entropy, (void *)b->d_scan, (void *)b->d_stats,
+                        (void *)b->d_host_cls, (void *)b->d_plane_job_slot, (void *)b->d_plane_jobs, (void *)b->d_image_jobs})
+            if (d) hipFree(d);
+        for (void *h : {(void *)b->h_expand_jobs, (void *)b->h_entropy, (void *)b->h_entropy_out, (void *)b->h_bounce, (void *)b->h_scan, (void *)b->h_host_cls})
+            if (h) hipHostFree(h);
+        for (hipEvent_t e : {b->expand_sent, b->entropy_uploaded, b->entropy_filled, b->ev0, b->ev1, b->enqueued})
+            if (e) hipEventDestroy(e);
         for (auto &e : b->cls_sent)
             if (e) hipEventDestroy(e);
         for (auto &e : b->ev_phase)
             if (e) hipEventDestroy(e);
-        if (b->d_plane_jobs) hipFree(b->d_plane_jobs);
-        if (b->d_image_jobs) hipFree(b->d_image_jobs);
+        b->o.free();
         b->scaled.free();
         b->win.free();
         for (FusedPlan &fp : b->fused) fused_free(fp);
-        if (b->ev0) hipEventDestroy(b->ev0);
-        if (b->ev1) hipEventDestroy(b->ev1);
-        if (b->enqueued) hipEventDestroy(b->enqueued);
     }
     delete b;
 }
@@ -931,6 +611,10 @@ int jpgpu::copy_device_to_pinned_host(void *host_pinned, const void *d_src, size
     return hipMemcpyAsync(host_pinned, d_src, bytes, hipMemcpyDeviceToHost, (hipStream_t)hip_stream) == hipSuccess ? JPGPU_OK : JPGPU_ERR_IO;
 }
 
+int jpgpu::batch_create_with(int device, const jpgpu_image_desc *descs, const jpgpu_window *windows, const jpgpu_placement *placements, uint32_t n_images,
+                             const OutputSpec &spec, jpgpu_batch **out) {
+    return batch_create(device, descs, windows, placements, n_images, JPGPU_BATCH_DEFAULT, spec, out);
+}
 // What jpgpu_batch_create_windowed would make of window `wn` on an image of descriptor `d`, without a batch (window_rule,
 // batch_layout.hpp): the pipeline sorts images out one by one before it forms sub-batches (a batch fails creation as a whole).
 int jpgpu::batch_check_window(const jpgpu_image_desc &d, const jpgpu_window &wn, bool &windowed, uint32_t &gw, uint32_t &gh, std::string &why) {
@@ -946,18 +630,14 @@ int jpgpu::batch_check_window(const jpgpu_image_desc &d, const jpgpu_window &wn,
 // one, are JPGPU_ERR_UNSUPPORTED too; one that shows no pixel is JPGPU_ERR_FORMAT.  Nothing is changed then.
 int jpgpu::batch_rewindow(jpgpu_batch *b, const jpgpu_window *windows, const jpgpu_placement *placements) {
     if (!b || !windows) return JPGPU_ERR_FORMAT;
-    if ((!b->own_out && !b->rs_w) || b->win.empty()) return JPGPU_ERR_UNSUPPORTED;  // (with an output size the windows' bytes are the batch's own)
+    OutputStage &o = b->o;
+    const bool sized = o.spec.sized();
+    if ((!b->own_out && !sized) || b->win.empty()) return JPGPU_ERR_UNSUPPORTED;  // (with an output size the windows' bytes are the batch's own)
     std::vector<jpgpu_placement> pls;
     if (placements) {
         bool any = false;
-        pls.assign(placements, placements + b->descs.size());
-        for (jpgpu_placement &pl : pls) {
-            if (pl.rw == 0 || pl.rh == 0) pl = jpgpu_placement{(uint16_t)b->rs_w, (uint16_t)b->rs_h, 0, 0};
-            uint32_t first, count, v0;
-            if (!placed_axis(pl.rw, pl.x, b->rs_w, first, count, v0) || !placed_axis(pl.rh, pl.y, b->rs_h, first, count, v0)) return JPGPU_ERR_FORMAT;
-            any = any || pl.rw != b->rs_w || pl.rh != b->rs_h || pl.x != 0 || pl.y != 0;
-        }
-        if (any != b->placed) return JPGPU_ERR_UNSUPPORTED;
+        if (normalise_placements(placements, (uint32_t)b->descs.size(), o.spec.w, o.spec.h, pls, any) < b->descs.size()) return JPGPU_ERR_FORMAT;
+        if (any != o.placed) return JPGPU_ERR_UNSUPPORTED;
     }
     std::vector<WindowGeom> geoms;
     std::vector<size_t> lens;
@@ -966,9 +646,9 @@ int jpgpu::batch_rewindow(jpgpu_batch *b, const jpgpu_window *windows, const jpg
     rc = use_device(b->device, b->err);
     if (rc) return rc;
     // (with an output size the windows' bytes live in the intermediate arena: the resized arena never changes)
-    size_t &w_bytes = b->rs_w ? b->pix_bytes : b->out_bytes, &w_cap = b->rs_w ? b->pix_cap : b->out_cap;
-    uint8_t *&w_arena = b->rs_w ? b->d_pix : b->d_out;
-    w_bytes = b->rs_w ? arena_layout(lens, b->pix_off, b->pix_len) : arena_layout(lens, b->out_off, b->out_len);
+    size_t &w_bytes = sized ? o.pix_bytes : b->out_bytes, &w_cap = sized ? o.pix_cap : b->out_cap;
+    uint8_t *&w_arena = sized ? o.d_pix : b->d_out;
+    w_bytes = sized ? arena_layout(lens, o.pix_off, o.pix_len) : arena_layout(lens, b->out_off, b->out_len);
     b->jobs_dirty = true;  // (every job's output pointer, the fused plans' included)
     B_HIP(batch_wait_enqueued(b));  // (idle by contract: the event has completed)
     if (w_bytes > w_cap) {
@@ -976,13 +656,12 @@ int jpgpu::batch_rewindow(jpgpu_batch *b, const jpgpu_window *windows, const jpg
         B_HIP(grow_device(w_arena, w_cap, w_bytes, arena_headroom(w_bytes, arena_layout(b->out_full_len))));
     }
     B_HIP(b->win.set_geoms(geoms, b->descs));
-    if (b->placed && placements) b->pl = pls;
-    if (b->rs_w) return batch_resample_tables(b);
-    return JPGPU_OK;
+    if (o.placed && placements) o.pl = pls;
+    return sized ? output_retable(b) : JPGPU_OK;
 }
 // bytes the output arena of the batch would hold without any window (what a pinned copy of it never needs more than)
 size_t jpgpu::batch_out_arena_bound(const jpgpu_batch *b) {
-    if (b && b->rs_w) return b->out_bytes;  // (an output size: the arena never changes)
+    if (b && b->o.spec.sized()) return b->out_bytes;  // (an output size: the arena never changes)
     return arena_layout(b ? b->out_full_len : std::vector<size_t>());
 }
 bool jpgpu::batch_image_windowed(const jpgpu_batch *b, uint32_t image) {
@@ -1087,29 +766,8 @@ int jpgpu_batch_decode(jpgpu_batch *b, void *hip_stream) {
     if (!b->win.empty())  // (windows: after the others)
         B_HIP(launch_window_band(b->win.d_geoms, b->win.d_image_jobs, b->win.d_plane_jobs, (uint32_t)b->win.ids.size(), b->win.max_tiles_x, b->win.max_bands,
                                  b->win.lds_bytes, b->win.scales, s));
-    if (b->tn_es && b->tn_sent) B_HIP(hipStreamWaitEvent(s, b->tn_sent, 0));  // (the jobs may have gone up on another stream than this one)
-    const bool rgb_out = (b->flags & JPGPU_BATCH_RGB_OUTPUT) != 0;
-    const bool rs_tensor = b->tn_es && !b->warp;  // (a warped batch resamples to u8, whatever it writes in the end)
-    if (b->placed && rs_tensor)  // (placements: the kernels of placed.hip, for this batch only)
-        B_HIP(launch_resample_placed_tensor(b->d_ptn_jobs, b->d_rs_tab, b->d_tn_table, b->tn_es, (uint32_t)b->descs.size(), b->rs_max_bands, b->rs_lds_bytes, s, rgb_out));
-    else if (b->placed)
-        B_HIP(launch_resample_placed(b->d_pl_jobs, b->d_rs_tab, (uint32_t)b->descs.size(), b->rs_max_bands, b->rs_lds_bytes, s, rgb_out));
-    else if (rs_tensor)  // (a tensor output: the same resample, its vertical pass writes every image's tensor)
-        B_HIP(launch_resample_tensor(b->d_tn_jobs, b->d_rs_tab, b->d_tn_table, b->tn_es, (uint32_t)b->descs.size(), b->rs_max_bands, b->rs_lds_bytes, s,
-                                      (b->flags & JPGPU_BATCH_RGB_OUTPUT) != 0));
-    else if (b->rs_w)  // (an output size: every image's pixels, wherever the launches above left them in the intermediate arena)
-        B_HIP(launch_resample_band(b->d_rs_jobs, b->d_rs_tab, (uint32_t)b->descs.size(), b->rs_max_bands, b->rs_lds_bytes, s, (b->flags & JPGPU_BATCH_RGB_OUTPUT) != 0));
-    if (b->rs_max_runs && !b->placed) {  // (the images whose bands go in runs: their own launch, beside the band launch above)
-        const uint32_t n_rs = (uint32_t)b->descs.size();
-        if (rs_tensor) B_HIP(launch_resample_tensor_run(b->d_tn_jobs + n_rs, b->d_rs_tab, b->d_tn_table, b->d_rs_bpr, b->tn_es, n_rs, b->rs_max_runs, b->rs_lds_bytes, s));
-        else B_HIP(launch_resample_run(b->d_rs_jobs + n_rs, b->d_rs_tab, b->d_rs_bpr, n_rs, b->rs_max_runs, b->rs_lds_bytes, s));
-    }
-    if (b->warp) {  // (the warp: behind the resample on the same stream, from the second intermediate arena into the output arena)
-        const uint32_t tiles = (b->rs_w * b->rs_h + WP_NT - 1u) / WP_NT;
-        const int32_t *tabs = reinterpret_cast<const int32_t *>(b->d_wp_jobs + b->descs.size() * sizeof(WarpJob));
-        if (b->wp_sent) B_HIP(hipStreamWaitEvent(s, b->wp_sent, 0));  // (the jobs may have gone up on another stream than this one)
-        B_HIP(launch_warp(reinterpret_cast<const WarpJob *>(b->d_wp_jobs), tabs, b->d_tn_table, b->tn_es, (uint32_t)b->descs.size(), tiles, s));
-    }
+    rc = output_launch(b, s);  // (an output size: the resample and what follows it)
+    if (rc) return rc;
     if (b->phase_events_valid) B_HIP(hipEventRecord(b->ev_phase[5], s));
     B_HIP(batch_mark_enqueued(b, s));
     return JPGPU_OK;

@@ -1,5 +1,5 @@
-// batch_internal.hpp — struct jpgpu_batch and the helpers that batch.cpp (creation, job tables, decode) and batch_entropy.cpp
-// (the device entropy and progressive launches) share.  Internal to those two translation units.
+// batch_internal.hpp — struct jpgpu_batch and the helpers that batch.cpp (creation, job tables, decode), batch_output.cpp (the
+// fixed-output stage) and batch_entropy.cpp (the device entropy and progressive launches) share.  Internal to those translation units.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -11,6 +11,7 @@
 #include <vector>
 
 #include "batch_layout.hpp"
+#include "batch_output.hpp"
 #include "compact.hpp"
 #include "fused.hpp"
 #include "fused_entries.hpp"
@@ -19,10 +20,6 @@
 #include "huff.hpp"
 #include "kernels.hpp"
 #include "range_stats.hpp"
-#include "resample_band.hpp"
-#include "tensor_band.hpp"
-#include "placed_band.hpp"
-#include "warp_band.hpp"
 #include "window_band.hpp"
 
 using namespace jpgpu;
@@ -83,6 +80,53 @@ struct BandGroup {
     }
 };
 
+// The fixed-output stage of a batch (batch_output.hpp: the options, the rules, the route; batch_output.cpp: the code).  With an output size
+// the output arena (d_out, out_off, out_len, out_bytes) holds h x w x channels elements per image, and every pixel kernel writes what it
+// always writes — the window's or the whole image's pixels — into an intermediate arena the batch owns (d_pix), which the route's resample
+// launch reads.  `d_jobs` holds the route's device records: ResampleJobs or TensorJobs (2 n: [0, n) for the band launch, [n, 2 n) the real
+// jobs of the images whose bands go in runs — bpr[i] != 0, the band launch sees such an image with no band), PlacedJobs or
+// PlacedTensorJobs (n: `jobs[i]` is then the job of image i's visible rectangle, places[i] where it lies).  Tensor records, and a warp's
+// WarpJobs with the N-sep tables behind them ([n WarpJob | n x (w + h) int32]), travel from pinned mirrors on the decode's stream: fresh
+// flips and matrices come with every call of a loader.  A warp reads a second arena (d_wsrc), which the u8 resample then writes.
+struct OutputStage {
+    OutputSpec spec;
+    OutputRoute route;
+    std::vector<size_t> pix_off, pix_len, wsrc_off;  // the intermediate arena, the warp's source arena
+    size_t pix_bytes = 0, pix_cap = 0;
+    uint8_t *d_pix = nullptr, *d_wsrc = nullptr;
+    std::vector<ResampleJob> jobs;  // per image
+    std::vector<int32_t> tab;       // the images' tables (equal axes share one)
+    std::vector<uint32_t> bpr;      // per image: bands per run (0: the image keeps its bands)
+    int32_t *d_tab = nullptr;
+    size_t tab_cap = 0;             // int32 words behind d_tab
+    uint32_t *d_bpr = nullptr;
+    void *d_tn_table = nullptr;     // 4 x 256 elements
+    uint32_t max_bands = 0, max_runs = 0, lds_bytes = 0;  // (max_bands over the images that keep their bands, max_runs over the others)
+    bool placed = false;            // for the batch's lifetime: other device records, another launch
+    std::vector<jpgpu_placement> pl;  // per image, normalised (normalise_placements)
+    std::vector<Place> places;        // per image
+    void *d_jobs = nullptr, *h_jobs = nullptr;
+    uint8_t *d_wp_jobs = nullptr, *h_wp_jobs = nullptr;
+    hipEvent_t tn_sent = nullptr, wp_sent = nullptr;  // behind the last copy out of each mirror
+    std::vector<uint8_t> flips;    // per image (jpgpu_batch_set_flips)
+    std::vector<jpgpu_warp> m;     // per image (jpgpu_batch_set_warps)
+    bool tn_dirty = false, wp_dirty = false;  // flips / matrices changed: the records go up before the next decode
+    void free() {
+        for (void *d : {(void *)d_pix, (void *)d_wsrc, (void *)d_tab, (void *)d_bpr, d_tn_table, d_jobs, (void *)d_wp_jobs})
+            if (d) (void)hipFree(d);
+        if (h_jobs) (void)hipHostFree(h_jobs);
+        if (h_wp_jobs) (void)hipHostFree(h_wp_jobs);
+        if (tn_sent) (void)hipEventDestroy(tn_sent);
+        if (wp_sent) (void)hipEventDestroy(wp_sent);
+    }
+};
+// batch_output.cpp, what batch.cpp calls: at creation, on a refresh of the job tables, on a decode behind the pixel kernels, and for
+// other windows or placements (also the last step of creation).
+int output_create(jpgpu_batch *b);
+int output_bind(jpgpu_batch *b, hipStream_t stream, bool all);
+int output_launch(jpgpu_batch *b, hipStream_t s);
+int output_retable(jpgpu_batch *b);
+
 struct jpgpu_batch {
     int device = 0;
     uint32_t flags = 0;
@@ -120,61 +164,7 @@ struct jpgpu_batch {
     // never in a fused plan, the scaled or the generic group.  Their coefficients are whole-image arena entries as ever, their output
     // is the window's bytes; the kernel works with exact arithmetic at every scale, so their range classes play no part.
     BandGroup<WindowGeom> win;
-    // A fixed output size (jpgpu_batch_create_resized, resample_band.hpp; rs_w == 0: none).  The output arena (d_out, out_off, out_len,
-    // out_bytes) then holds rs_h x rs_w x ncomp bytes per image, and every pixel kernel above writes what it always writes — the window's
-    // or the whole image's pixels — into an intermediate arena the batch owns (d_pix, pix_off, pix_len), which one more launch resamples.
-    uint32_t rs_w = 0, rs_h = 0;
-    uint32_t filter = 0;  // the resample filter (JPGPU_BATCH_FILTER bits of the flags): every table of the batch is made with it
-    std::vector<size_t> pix_off, pix_len;
-    size_t pix_bytes = 0, pix_cap = 0;
-    uint8_t *d_pix = nullptr;
-    std::vector<ResampleJob> rs_jobs;  // per image
-    std::vector<int32_t> rs_tab;       // the images' tables (equal axes share one)
-    ResampleJob *d_rs_jobs = nullptr;
-    int32_t *d_rs_tab = nullptr;
-    size_t rs_tab_cap = 0;             // int32 words behind d_rs_tab
-    uint32_t rs_max_bands = 0, rs_lds_bytes = 0;
-    // Runs of bands (resample_band.hpp): rs_bpr[i] != 0 — image i's bands go, rs_bpr[i] at a time, to the workgroups of a
-    // second launch (resample_run_kernel / resample_tensor_run_kernel) and the band launch sees the image with no band.  The device job
-    // arrays hold 2 n entries: [0, n) for the band launch, [n, 2 n) the images' real jobs for the run launch.  rs_max_bands is over the
-    // images that keep their bands, rs_max_runs over the others (0: no run launch; never with placements or BILINEAR).
-    std::vector<uint32_t> rs_bpr;
-    uint32_t *d_rs_bpr = nullptr;
-    uint32_t rs_max_runs = 0;
-    // A tensor output (jpgpu_batch_create_tensor, tensor_band.hpp; tn_es == 0: none): an output size whose resample launch writes the
-    // normalised CHW tensor of every image instead of its resized pixels.  The output arena holds ncomp x rs_h x rs_w elements per image;
-    // the planner, the tables and rs_jobs are the output size's, the device jobs are TensorJobs (rs_jobs[i] + the image's flip).
-    uint32_t tn_es = 0;                // bytes per element
-    std::vector<uint8_t> tn_flips;     // per image (jpgpu_batch_set_flips)
-    bool tn_dirty = false;             // the flips changed: the TensorJobs go up before the next decode
-    TensorJob *d_tn_jobs = nullptr;
-    TensorJob *h_tn_jobs = nullptr;    // pinned mirror the jobs travel from, on the decode's stream
-    hipEvent_t tn_sent = nullptr;      // behind the last copy out of the mirror
-    void *d_tn_table = nullptr;        // 4 x 256 elements
-    // Placements (jpgpu_batch_create_placed, placed_band.hpp; placed == false: none): some image of a batch with an output size is resampled
-    // to a size of its own and laid into the output with cropping / fill.  rs_jobs[i] is then the job of image i's visible rectangle (tables
-    // of the visible range), rs_places[i] where it lies; the device jobs are PlacedJobs / PlacedTensorJobs and the launch is placed.hip's.
-    bool placed = false;
-    std::vector<jpgpu_placement> pl;   // per image, "none" written out as (rs_w, rs_h, 0, 0)
-    uint32_t pl_fill = 0;              // fill[c] in byte c
-    std::vector<Place> rs_places;      // per image
-    PlacedJob *d_pl_jobs = nullptr;
-    PlacedTensorJob *d_ptn_jobs = nullptr;
-    PlacedTensorJob *h_ptn_jobs = nullptr;  // pinned mirror, as h_tn_jobs
-    // A warp (jpgpu_batch_create_warped, warp_band.hpp; warp == false: none): the resample launch is the u8 one of the same arguments —
-    // band, run or placed, whatever tn_es says — and writes a second intermediate arena the batch owns (d_wsrc, wsrc_off: rs_h x rs_w x nc
-    // bytes per image); one launch behind it reads that arena through every image's matrix and writes the output arena, pixels or (tn_es)
-    // tensors.  The WarpJobs and the N-sep tables behind them ([n WarpJob | n x (rs_w + rs_h) int32]) travel from a pinned mirror on the
-    // decode's stream, as the TensorJobs do: fresh matrices and flips come with every call of a loader.
-    bool warp = false;
-    uint32_t wp_filter = 0;            // JPGPU_WARP_*
-    uint32_t wp_fill = 0;              // wfill[c] in byte c
-    std::vector<jpgpu_warp> wp_m;      // per image (jpgpu_batch_set_warps)
-    bool wp_dirty = false;             // matrices or flips changed: the WarpJobs go up before the next decode
-    std::vector<size_t> wsrc_off;
-    uint8_t *d_wsrc = nullptr;
-    uint8_t *d_wp_jobs = nullptr, *h_wp_jobs = nullptr;
-    hipEvent_t wp_sent = nullptr;      // behind the last copy out of the mirror
+    OutputStage o;  // a fixed output size and what follows it (o.spec.w == 0: none)
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
     // Behind the last work enqueued on a caller's stream that reads the batch's tables or its coefficient arena (every decode,
     // jpgpu_batch_classify_on_device).  That stream may be a non-blocking one, which a blocking copy on the null stream does not order
@@ -255,8 +245,8 @@ static hipError_t batch_mark_enqueued(jpgpu_batch *b, hipStream_t s) {
 }
 
 // where the pixel kernels write: the output arena, or the intermediate one of a batch with an output size
-static uint8_t *pix_base(const jpgpu_batch *b) { return b->rs_w ? b->d_pix : b->d_out; }
-static const std::vector<size_t> &pix_offsets(const jpgpu_batch *b) { return b->rs_w ? b->pix_off : b->out_off; }
+static uint8_t *pix_base(const jpgpu_batch *b) { return b->o.spec.w ? b->o.d_pix : b->d_out; }
+static const std::vector<size_t> &pix_offsets(const jpgpu_batch *b) { return b->o.spec.w ? b->o.pix_off : b->out_off; }
 
 // first use of the device-side classes: statistics (zeroed), class table, pinned staging
 static int batch_enable_dev_classes(jpgpu_batch *b) {

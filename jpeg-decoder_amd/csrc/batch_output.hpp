@@ -1,0 +1,113 @@
+// batch_output.hpp — the fixed-output stage of a batch stated once: its options as one record, the rules that
+// refuse a combination, the placement normalisation, the bytes an image takes in the stage's arenas, and the route — which launches
+// run.  batch.cpp, batch_output.cpp and pipeline.cpp share it.  No HIP dependency (tests/emu/emu_batch_output.cpp runs it on the CPU).
+#pragma once
+#include <string.h>
+
+#include "batch_layout.hpp"
+#include "placed_band.hpp"
+#include "resample_band.hpp"
+#include "tensor_band.hpp"
+#include "warp_band.hpp"
+
+namespace jpgpu {
+
+// What a batch is created with beyond its images, windows and placements.  An absent option holds its zero value.
+struct OutputSpec {
+    uint32_t w = 0, h = 0;              // the output size (0 x 0: none)
+    uint32_t filter = 0;                // JPGPU_FILTER_* (0: bilinear)
+    bool rgb = false;                   // JPGPU_BATCH_RGB_OUTPUT
+    bool tensor = false;                // a tensor format ...
+    jpgpu_tensor_format tn{};           // ... and which
+    uint8_t fill[4] = {0, 0, 0, 0};     // what a placement leaves uncovered
+    bool warp = false;                  // warp options ...
+    jpgpu_warp_options wp{};            // ... and which
+    bool sized() const { return w != 0 || h != 0; }
+    uint32_t elem_bytes() const { return tensor ? tensor_elem_bytes(tn.dtype) : 1u; }
+    uint32_t channels(uint32_t ncomp) const { return rgb ? 3u : ncomp; }
+};
+inline bool operator==(const OutputSpec &a, const OutputSpec &b) {
+    return a.w == b.w && a.h == b.h && a.filter == b.filter && a.rgb == b.rgb && a.tensor == b.tensor && a.tn.dtype == b.tn.dtype &&
+           a.tn.reserved == b.tn.reserved && memcmp(a.tn.mean, b.tn.mean, sizeof a.tn.mean) == 0 && memcmp(a.tn.std, b.tn.std, sizeof a.tn.std) == 0 &&
+           memcmp(a.fill, b.fill, 4) == 0 && a.warp == b.warp && a.wp.filter == b.wp.filter && memcmp(a.wp.fill, b.wp.fill, 4) == 0 &&
+           a.wp.reserved == b.wp.reserved;
+}
+inline uint32_t pack_fill(const uint8_t f[4]) { return (uint32_t)f[0] | ((uint32_t)f[1] << 8) | ((uint32_t)f[2] << 16) | ((uint32_t)f[3] << 24); }
+
+// The rules of the options among themselves, before a device is touched.  A filter or RGB output without an output size is
+// JPGPU_ERR_UNSUPPORTED, everything else JPGPU_ERR_FORMAT; the reason in `why`.
+inline int output_rule(const OutputSpec &s, std::string &why) {
+    char msg[240];
+    const auto no = [&](int code, const char *fmt, uint32_t a, uint32_t b, uint32_t c = 0) { return snprintf(msg, sizeof msg, fmt, a, b, c), why = msg, code; };
+    if (s.sized() && (s.w == 0 || s.h == 0 || s.w > RS_MAX_OUT || s.h > RS_MAX_OUT))
+        return no(JPGPU_ERR_FORMAT, "output size %ux%u: width and height must be 1..%u", s.w, s.h, RS_MAX_OUT);
+    if (s.filter >= RS_FILTERS) return no(JPGPU_ERR_FORMAT, "resample filter %u: the ids are 0..%u (JPGPU_FILTER_*)", s.filter, RS_FILTERS - 1u);
+    if (s.filter && !s.sized()) return why = std::string("a resample filter (") + resample_filter_name(s.filter) + ") needs an output size", JPGPU_ERR_UNSUPPORTED;
+    if (s.rgb && !s.sized()) return why = "RGB output (JPGPU_BATCH_RGB_OUTPUT) needs an output size", JPGPU_ERR_UNSUPPORTED;
+    if (s.warp && !s.sized()) return why = "a warp needs an output size", JPGPU_ERR_FORMAT;
+    if (s.warp && (s.wp.filter > WP_BILINEAR || s.wp.reserved != 0))
+        return no(JPGPU_ERR_FORMAT, "warp options: filter %u, reserved %u (JPGPU_WARP_NEAREST or JPGPU_WARP_BILINEAR, reserved 0)", s.wp.filter, s.wp.reserved);
+    if (s.tensor && !s.sized()) return why = "a tensor format needs an output size", JPGPU_ERR_FORMAT;
+    if (s.tensor && (tensor_elem_bytes(s.tn.dtype) == 0 || s.tn.reserved != 0))
+        return no(JPGPU_ERR_FORMAT, "tensor format: dtype %u, reserved %u (dtype must be 1..3, reserved 0)", s.tn.dtype, s.tn.reserved);
+    return JPGPU_OK;
+}
+// The rules of the options against one image of `ncomp` components.  Its tensor format's means and stds against its channels (no device
+// is needed for that: batch_create asks first); then all of them, under the colour function `color_fn` (ImageJob::color_fn).
+inline int output_tensor_rule(const OutputSpec &s, uint32_t ncomp, std::string &why) {
+    const char *bad = nullptr;
+    if (s.tensor && !tensor_format_ok(s.tn.dtype, s.tn.reserved, s.tn.mean, s.tn.std, s.channels(ncomp), bad)) return why = std::string("tensor format: ") + bad, JPGPU_ERR_FORMAT;
+    return JPGPU_OK;
+}
+inline int output_image_rule(const OutputSpec &s, uint32_t ncomp, uint32_t color_fn, std::string &why) {
+    if (s.sized() && color_fn == CC_NONE && ncomp > 1)
+        return why = "no output size for planar output (ColorTransform None with more than one component)", JPGPU_ERR_UNSUPPORTED;
+    if (s.rgb && ncomp != 1 && ncomp != 3 && ncomp != 4) return why = "no RGB output for " + std::to_string(ncomp) + " components", JPGPU_ERR_UNSUPPORTED;
+    return output_tensor_rule(s, ncomp, why);
+}
+
+// Placements as a batch keeps them: "none" (rw == 0 or rh == 0) written out as the whole w x h output; `placed`: one differs from the
+// whole output.  Returns n, or the index of the first image whose placement shows no pixel (`out` is then of no use).
+inline uint32_t normalise_placements(const jpgpu_placement *pls, uint32_t n, uint32_t w, uint32_t h, std::vector<jpgpu_placement> &out, bool &placed) {
+    out.assign(pls, pls + n);
+    placed = false;
+    for (uint32_t i = 0; i < n; i++) {
+        jpgpu_placement &pl = out[i];
+        if (pl.rw == 0 || pl.rh == 0) pl = jpgpu_placement{(uint16_t)w, (uint16_t)h, 0, 0};
+        uint32_t first, count, v0;
+        if (!placed_axis(pl.rw, pl.x, w, first, count, v0) || !placed_axis(pl.rh, pl.y, h, first, count, v0)) return i;
+        placed = placed || pl.rw != w || pl.rh != h || pl.x != 0 || pl.y != 0;
+    }
+    return n;
+}
+
+// Bytes of one image of `ncomp` components in the output arena, or (`u8`) in the arena a warp reads: what the u8 batch's output would be.
+inline size_t output_image_bytes(const OutputSpec &s, uint32_t ncomp, bool u8 = false) {
+    return (size_t)s.w * s.h * s.channels(ncomp) * (u8 ? 1u : s.elem_bytes());
+}
+// ... of every image, laid out as an arena (batch_layout.hpp).  The intermediate arena is what the batch lays out without an output size.
+inline size_t output_arena(const OutputSpec &s, const std::vector<jpgpu_image_desc> &descs, bool u8, std::vector<size_t> &off, std::vector<size_t> &len) {
+    std::vector<size_t> lens(descs.size());
+    for (size_t i = 0; i < descs.size(); i++) lens[i] = output_image_bytes(s, descs[i].ncomp, u8);
+    return arena_layout(lens, off, len);
+}
+
+// The route: which resample launch runs, whether the launch of runs of bands goes beside it, whether a warp follows.  Allocation, job
+// upload and launch switch on it.
+enum class Resample : uint8_t { None, Band, Tensor, Placed, PlacedTensor };
+struct OutputRoute {
+    Resample resample = Resample::None;
+    bool runs = false, warp = false;
+    bool tensor_jobs() const { return resample == Resample::Tensor || resample == Resample::PlacedTensor; }
+};
+inline OutputRoute output_route(const OutputSpec &s, bool placed, uint32_t max_runs) {
+    OutputRoute r;
+    if (!s.sized()) return r;
+    r.warp = s.warp;
+    const bool tensor = s.tensor && !s.warp;  // (a warped batch resamples to u8, whatever it writes in the end)
+    r.resample = placed ? (tensor ? Resample::PlacedTensor : Resample::Placed) : (tensor ? Resample::Tensor : Resample::Band);
+    r.runs = max_runs != 0 && !placed;
+    return r;
+}
+
+}  // namespace jpgpu

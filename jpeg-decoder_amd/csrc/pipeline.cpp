@@ -20,12 +20,9 @@
 #include <thread>
 #include <vector>
 
-#include "batch_layout.hpp"
+#include "batch_output.hpp"
 #include "compact.hpp"
 #include "host/frontend.hpp"
-#include "host_common.hpp"
-#include "tensor_band.hpp"
-#include "warp_band.hpp"
 
 using jpgpu::host::DecodeError;
 using jpgpu::host::Frontend;
@@ -38,18 +35,19 @@ constexpr uint32_t kCopyStreams = 4, kD2HStreams = 2;
 // Default pool size: one thread per physical core (SMT siblings plus the uploader thread made 256 threads slower and
 // erratic on the 2 x 64-core host), but no more than twice the CPUs a cgroup quota grants the process: with
 // cpu.max = 16 CPUs, 32 threads sustained 3.8 k 1080p images/s, 128 threads 2.9 k (throttled mid-image).
-uint32_t default_threads() {
-    uint32_t n = std::max(1u, std::thread::hardware_concurrency() / 2u);
+unsigned long cgroup_cpus() {  // the CPUs a cgroup quota grants the process, rounded up (0: no quota)
+    unsigned long cpus = 0, period = 0;
     if (FILE *f = fopen("/sys/fs/cgroup/cpu.max", "r")) {
         char quota[32] = {0};
-        unsigned long period = 0;
-        if (fscanf(f, "%31s %lu", quota, &period) == 2 && strcmp(quota, "max") != 0 && period > 0) {
-            const unsigned long cpus = (strtoul(quota, nullptr, 10) + period - 1) / period;
-            if (cpus > 0) n = std::min<uint32_t>(n, (uint32_t)std::max(2ul, 2ul * cpus));
-        }
+        if (fscanf(f, "%31s %lu", quota, &period) == 2 && strcmp(quota, "max") != 0 && period > 0) cpus = (strtoul(quota, nullptr, 10) + period - 1) / period;
         fclose(f);
     }
-    return n;
+    return cpus;
+}
+uint32_t default_threads() {
+    const uint32_t n = std::max(1u, std::thread::hardware_concurrency() / 2u);
+    const unsigned long cpus = cgroup_cpus();
+    return cpus ? std::min<uint32_t>(n, (uint32_t)std::max(2ul, 2ul * cpus)) : n;
 }
 
 // CPUs the process may really use: its affinity mask, capped by a cgroup quota (the progressive dispatcher's host side)
@@ -58,16 +56,8 @@ uint32_t granted_cpus() {
     cpu_set_t set;
     CPU_ZERO(&set);
     if (sched_getaffinity(0, sizeof(set), &set) == 0) n = std::min<uint32_t>(n, (uint32_t)std::max(1, CPU_COUNT(&set)));
-    if (FILE *f = fopen("/sys/fs/cgroup/cpu.max", "r")) {
-        char quota[32] = {0};
-        unsigned long period = 0;
-        if (fscanf(f, "%31s %lu", quota, &period) == 2 && strcmp(quota, "max") != 0 && period > 0) {
-            const unsigned long cpus = (strtoul(quota, nullptr, 10) + period - 1) / period;
-            if (cpus > 0) n = std::min<uint32_t>(n, (uint32_t)cpus);
-        }
-        fclose(f);
-    }
-    return n;
+    const unsigned long cpus = cgroup_cpus();
+    return cpus ? std::min<uint32_t>(n, (uint32_t)cpus) : n;
 }
 
 double now_ms() {
@@ -225,6 +215,12 @@ private:
     std::unique_ptr<jpgpu::CompactWriter> writer_[4];
 };
 
+struct Nothing : RowSink {  // a sink that keeps nothing: for streams that are decoded only to hear what they throw
+    void start(uint32_t, const jpgpu_component &, const uint16_t *) override {}
+    void append_row(uint32_t, const int16_t *, size_t) override {}
+    void finish(uint32_t, uint32_t) override {}
+};
+
 // Finished images are handed to one uploader thread: hipMemcpyAsync calls from hundreds of threads contend in the
 // runtime, one caller keeps the copy queues busy.  skip = the image failed and will never be uploaded.
 struct UploadQueue {
@@ -258,18 +254,11 @@ struct SubBatch {
     bool compact = false;             // layout of h_coef: compact regions (stage_off) or a mirror of the arena
     std::vector<size_t> stage_off;    // compact mode: [image*4 + comp] offset of the component's region in h_coef
     std::vector<jpgpu_window> wins;   // the window of every image as the batch was created with it (w == 0: none); empty: no image has one
-    uint16_t rs_w = 0, rs_h = 0;      // the output size the batch was created with (jpgpu_pipeline_set_output_size; 0 x 0: none)
-    bool tensor = false;              // the tensor format the batch was created with (jpgpu_pipeline_set_tensor_output), if any
-    jpgpu_tensor_format tn{};
-    bool rgb = false;                 // created with JPGPU_BATCH_RGB_OUTPUT (jpgpu_pipeline_set_rgb_output)
-    uint32_t filter = 0;              // created with JPGPU_BATCH_FILTER(filter) (jpgpu_pipeline_set_filter)
+    jpgpu::OutputSpec made_with;      // the output options the batch was created with (jpgpu_pipeline::out) ...
+    jpgpu_fit fit{};                  // ... and the fit rule its placements come from (jpgpu_pipeline::fit)
     std::vector<uint8_t> flips;       // a tensor batch: the flip of every image as the batch holds it (jpgpu_batch_set_flips)
-    bool fit_on = false;              // created with placements under this rule (jpgpu_pipeline_set_fit)
-    jpgpu_fit fit{};
-    std::vector<jpgpu_placement> pls; // ... the placement of every image as the batch holds it
-    bool warp_on = false;             // created with these warp options (jpgpu_pipeline_set_warp)
-    jpgpu_warp_options warp_opt{};
-    std::vector<jpgpu_warp> warps;    // ... the matrix of every image as the batch holds it (jpgpu_batch_set_warps)
+    std::vector<jpgpu_placement> pls; // a fit: the placement of every image as the batch holds it
+    std::vector<jpgpu_warp> warps;    // a warp: the matrix of every image as the batch holds it (jpgpu_batch_set_warps)
     uint32_t remaining = 0;  // images not yet uploaded / failed (uploader thread only)
     hipEvent_t ready[kCopyStreams] = {nullptr, nullptr, nullptr, nullptr};
     hipEvent_t decoded = nullptr;  // recorded on the compute stream behind the sub-batch's pixel kernels: downloads and the gather wait for it
@@ -283,16 +272,10 @@ struct SubBatch {
         descs.clear();
         stage_off.clear();
         wins.clear();
-        rs_w = rs_h = 0;
-        tensor = false;
-        rgb = false;
-        filter = 0;
-        flips.clear();
-        fit_on = false;
+        made_with = jpgpu::OutputSpec{};
         fit = jpgpu_fit{};
+        flips.clear();
         pls.clear();
-        warp_on = false;
-        warp_opt = jpgpu_warp_options{};
         warps.clear();
     }
 };
@@ -334,15 +317,9 @@ struct jpgpu_pipeline {
     // download held back the kernels of the next sub-batch that shares the stream, and the copies of a call did not run back to back)
     hipStream_t d2h[kD2HStreams] = {};
     uint16_t req_w = 0, req_h = 0;  // jpgpu_pipeline_set_scale (0 x 0: full size)
-    uint16_t rs_w = 0, rs_h = 0;    // jpgpu_pipeline_set_output_size (0 x 0: none)
-    bool tensor = false;            // jpgpu_pipeline_set_tensor_output
-    bool rgb = false;               // jpgpu_pipeline_set_rgb_output
-    uint32_t filter = 0;            // jpgpu_pipeline_set_filter (JPGPU_FILTER_*; 0: bilinear)
-    bool fit_on = false;            // jpgpu_pipeline_set_fit (a rule other than stretch)
-    jpgpu_fit fit{};
-    bool warp_on = false;           // jpgpu_pipeline_set_warp
-    jpgpu_warp_options warp_opt{};
-    jpgpu_tensor_format tn{};
+    jpgpu::OutputSpec out;          // jpgpu_pipeline_set_output_size / _tensor_output / _rgb_output / _filter / _warp, and the fit's fill
+    jpgpu_fit fit{};                // jpgpu_pipeline_set_fit (zeros — stretch — without one: every placement is the whole output)
+    bool fit_on() const { return fit.mode != JPGPU_FIT_STRETCH; }
     int color_transform = -1;       // jpgpu_pipeline_set_color_transform (< 0: what every image says itself)
     size_t max_bytes = SIZE_MAX;    // jpgpu_pipeline_set_max_decoding_buffer_size
     uint32_t n_compute = kComputeStreamsDefault;  // streams in use (JPGPU_PIPE_STREAMS: tuning knob, up to kComputeStreams)
@@ -397,8 +374,6 @@ static void pin_to(const std::vector<int> &cpus) {
     (void)sched_setaffinity(0, sizeof(set), &set);  // (best effort: a refused mask leaves the thread where it was)
 }
 
-// An image the device entropy decoder handed back: the pinned behaviour is the host decoder's — decode it here (uploader
-// thread; rare) and upload it densely, or record the error it raises.
 // An image the device entropy decoder handed back: decode it on the host (dense planes, plain upload).  Two steps so that
 // several of them can be decoded side by side: host_redecode_stage (any thread), host_redecode_upload (the uploader).
 struct Redecode {
@@ -646,206 +621,145 @@ static uint32_t progressive_share_for_the_device(jpgpu_pipeline *p, const uint8_
 int jpgpu_pipeline_decode(jpgpu_pipeline *p, const uint8_t *const *data, const size_t *len, uint32_t n, uint32_t flags) {
     return jpgpu_pipeline_decode_windowed(p, data, len, nullptr, n, flags);
 }
-
-int jpgpu_pipeline_decode_windowed(jpgpu_pipeline *p, const uint8_t *const *data, const size_t *len, const jpgpu_window *windows, uint32_t n,
-                                   uint32_t flags) {
+int jpgpu_pipeline_decode_windowed(jpgpu_pipeline *p, const uint8_t *const *data, const size_t *len, const jpgpu_window *windows, uint32_t n, uint32_t flags) {
     return jpgpu_pipeline_decode_augmented(p, data, len, windows, nullptr, n, flags);
 }
-
 int jpgpu_pipeline_decode_augmented(jpgpu_pipeline *p, const uint8_t *const *data, const size_t *len, const jpgpu_window *windows, const uint8_t *flips,
                                     uint32_t n, uint32_t flags) {
     return jpgpu_pipeline_decode_warped(p, data, len, windows, flips, nullptr, n, flags);
 }
+}  // extern "C"
 
-int jpgpu_pipeline_decode_warped(jpgpu_pipeline *p, const uint8_t *const *data, const size_t *len, const jpgpu_window *windows, const uint8_t *flips,
-                                 const jpgpu_warp *warps, uint32_t n, uint32_t flags) {
-    jpgpu::TraceRange roctx_range("jpgpu_pipeline_decode");
-    // (unknown bits are refused, not ignored: 8u was round 2-3's JPGPU_PIPELINE_PROGRESSIVE_DELTAS, removed in round 4 — a caller built
-    // against that header would otherwise silently get another transport: ADVICE r4)
-    constexpr uint32_t kKnownFlags = JPGPU_PIPELINE_DOWNLOAD | JPGPU_PIPELINE_DENSE | JPGPU_PIPELINE_DEVICE_ENTROPY | JPGPU_PIPELINE_GATHER |
-                                     JPGPU_PIPELINE_HOST_LIGHT | JPGPU_PIPELINE_HOST_STAGED | JPGPU_PIPELINE_INPUT_PINNED | JPGPU_PIPELINE_PROGRESSIVE_ON_HOST;
-    if (p && (flags & ~kKnownFlags)) return jpgpu::set_err(p->err, JPGPU_ERR_FORMAT, "jpgpu_pipeline_decode: unknown flag bits 0x%x (this library: %s)", flags & ~kKnownFlags, jpgpu_version());
-    // (a tensor output needs an output size, flips a tensor output: refused before anything is decoded)
-    if (p && p->tensor && !p->rs_w) return jpgpu::set_err(p->err, JPGPU_ERR_FORMAT, "jpgpu_pipeline_decode: a tensor output needs an output size (jpgpu_pipeline_set_output_size)");
-    if (p && p->rgb && !p->rs_w) return jpgpu::set_err(p->err, JPGPU_ERR_FORMAT, "jpgpu_pipeline_decode: RGB output needs an output size (jpgpu_pipeline_set_output_size)");
-    if (p && p->filter && !p->rs_w) return jpgpu::set_err(p->err, JPGPU_ERR_FORMAT, "jpgpu_pipeline_decode: a resample filter needs an output size (jpgpu_pipeline_set_output_size)");
-    if (p && p->fit_on && !p->rs_w) return jpgpu::set_err(p->err, JPGPU_ERR_FORMAT, "jpgpu_pipeline_decode: a fit needs an output size (jpgpu_pipeline_set_output_size)");
-    if (p && flips && !p->tensor) return jpgpu::set_err(p->err, JPGPU_ERR_FORMAT, "jpgpu_pipeline_decode_augmented: flips need a tensor output (jpgpu_pipeline_set_tensor_output)");
-    if (p && p->warp_on && !p->rs_w) return jpgpu::set_err(p->err, JPGPU_ERR_FORMAT, "jpgpu_pipeline_decode: a warp needs an output size (jpgpu_pipeline_set_output_size)");
-    if (p && warps && !p->warp_on) return jpgpu::set_err(p->err, JPGPU_ERR_FORMAT, "jpgpu_pipeline_decode_warped: warps need warp options (jpgpu_pipeline_set_warp)");
-    if (p && !p->children.empty()) return (n && (!data || !len)) ? JPGPU_ERR_FORMAT : multi_decode(p, data, len, windows, flips, warps, n, flags);
-    if (!p || !p->pool || (n && (!data || !len))) return JPGPU_ERR_FORMAT;
-    if ((flags & JPGPU_PIPELINE_GATHER) && !p->gather_on) flags &= ~(uint32_t)JPGPU_PIPELINE_GATHER;  // (one device: the pixels are where a gather would put them)
-    int rc = jpgpu::use_device(p->device, p->err);
-    if (rc) return rc;
-    const double t0 = now_ms(), cpu0 = process_cpu_ms();
-    const bool download = (flags & JPGPU_PIPELINE_DOWNLOAD) != 0, compact = (flags & JPGPU_PIPELINE_DENSE) == 0;
-    const bool device_entropy = (flags & JPGPU_PIPELINE_DEVICE_ENTROPY) != 0;
-    const bool device_progressive = device_entropy && (flags & JPGPU_PIPELINE_PROGRESSIVE_ON_HOST) == 0 && !getenv("JPGPU_PIPE_PROGRESSIVE_ON_HOST");
-    p->n = n;
-    p->fes.clear();
-    p->fes.resize(n);
-    p->has_frame.assign(n, 0);
-    p->status.assign(n, JPGPU_ERR_INTERNAL);
-    p->errors.assign(n, std::string());
-    p->infos.assign(n, jpgpu_image_info{});
-    p->wins.assign(n, jpgpu_window{0, 0, 0, 0});
-    p->places.assign(n, jpgpu_placement{0, 0, 0, 0});
-    p->sub_of.assign(n, -1);
-    p->plans.clear();
-    p->plans.resize(n);
-    p->prog_plans.clear();
-    p->prog_plans.resize(n);
-    p->slot.assign(n, -1);
-    p->n_subs = 0;
-    p->downloaded = download;
-    p->path.clear();
-    p->t = jpgpu_pipeline_timings{};
-    p->t.threads = p->pool->size() + p->stage_pool->size();  // (+ one uploader thread per call, which mostly waits)
-    std::vector<jpgpu_image_desc> cand(n);
-    // Windows (jpgpu_pipeline_decode_windowed) are checked per image as soon as its header gives the output grid, before anything is
-    // dealt to sub-batches — a batch refuses a bad window for all of its images, here only the image concerned fails and leaves the
-    // call as an image whose header failed does.  win[i].w != 0 afterwards: image i runs the window kernel.
-    std::vector<jpgpu_window> win(windows ? n : 0u, jpgpu_window{0, 0, 0, 0});
-
-    // 1. headers
-    p->pool->run(n, [&](uint32_t i) {
-        try {
-            p->fes[i].reset(new Frontend(data[i], len[i], Frontend::Borrowed{}));
-            Frontend &fe = *p->fes[i];
-            read_info_with_options(p, fe);
-            p->infos[i] = fe.info();
-            jpgpu_image_desc d;
-            memset(&d, 0, sizeof(d));
-            d.ncomp = fe.ncomp();
-            for (uint32_t c = 0; c < d.ncomp; c++) {
-                d.components[c] = fe.components()[c];
-                for (int k = 0; k < 64; k++) d.quantization_tables[c][k] = 1;  // set once the scans are parsed
-            }
-            d.out_w = fe.output_width();
-            d.out_h = fe.output_height();
-            d.color_transform = fe.color_transform();
-            {
-                // A block costs at least two bits.  A header that announces far more blocks than the file can hold (truncated or
-                // hostile: 65535 x 65535 in 200 bytes) would have the sub-batch allocate gigabytes of arenas and pinned staging
-                // — 2.5 s for one such file — before the entropy decoder finds out: let it find out first, into a sink that
-                // keeps nothing.  (A stream that decodes after all goes on as usual.)
-                uint64_t blocks = 0;
-                for (uint32_t c = 0; c < d.ncomp; c++) blocks += (uint64_t)d.components[c].block_width * d.components[c].block_height;
-                if ((uint64_t)len[i] * 8u < blocks * 2u) {
-                    struct Nothing : RowSink {
-                        void start(uint32_t, const jpgpu_component &, const uint16_t *) override {}
-                        void append_row(uint32_t, const int16_t *, size_t) override {}
-                        void finish(uint32_t, uint32_t) override {}
-                    } nothing;
-                    Frontend probe(data[i], len[i], Frontend::Borrowed{});
-                    read_info_with_options(p, probe);
-                    probe.decode_to(nothing);  // throws what the image's decode() would throw
-                }
-            }
-            bool planar = false;  // color_no_convert with more than one component: planar within a row
-            {
-                // what compute_image would refuse for this frame (an impossible sampling combination, a colour function whose row
-                // copy would overrun: src/decoder.rs:1300-1336, src/upsampler.rs:20-45) fails THIS image here — a sub-batch is
-                // created from frames the pixel backend takes, one refused frame must not fail its neighbours
-                jpgpu::ImageJob probe;
-                uint8_t *no_planes[4] = {nullptr, nullptr, nullptr, nullptr};
-                size_t out_len = 0;
-                std::string why;
-                const int v = jpgpu::build_image_job(d.components, d.ncomp, no_planes, d.out_w, d.out_h, d.color_transform, nullptr, probe, out_len, why);
-                if (v != JPGPU_OK) {
-                    // (the reference decodes the entropy data before it gets to compute_image: a stream that is broken as well reports that)
-                    struct Nothing : RowSink {
-                        void start(uint32_t, const jpgpu_component &, const uint16_t *) override {}
-                        void append_row(uint32_t, const int16_t *, size_t) override {}
-                        void finish(uint32_t, uint32_t) override {}
-                    } nothing;
-                    Frontend whole(data[i], len[i], Frontend::Borrowed{});
-                    read_info_with_options(p, whole);
-                    whole.decode_to(nothing);
-                    throw DecodeError{v, why};
-                }
-                planar = probe.color_fn == jpgpu::CC_NONE && d.ncomp > 1;
-            }
-            cand[i] = d;
-            {
-                uint32_t gw = 0, gh = 0;
-                bool windowed = false;
-                std::string why;
-                const int v = jpgpu::batch_check_window(d, windows ? windows[i] : jpgpu_window{0, 0, 0, 0}, windowed, gw, gh, why);
-                if (v != JPGPU_OK) throw DecodeError{v, why};
-                p->wins[i] = jpgpu_window{0, 0, (uint16_t)gw, (uint16_t)gh};
-                if (windowed) win[i] = p->wins[i] = windows[i];
-                // (an output size: planar output has no resample — the image fails alone, like a refused window)
-                if (p->rs_w && planar)
-                    throw DecodeError{JPGPU_ERR_UNSUPPORTED, "no output size for planar output (ColorTransform None with more than one component)"};
-                if (p->rs_w) p->places[i] = jpgpu_placement{p->rs_w, p->rs_h, 0, 0};
-                // (a fit: the placement of THIS image's source — its window, else its output grid; a refused rule fails the image alone)
-                if (p->fit_on && jpgpu_fit_placement(&p->fit, p->wins[i].w, p->wins[i].h, p->rs_w, p->rs_h, &p->places[i]) != JPGPU_OK) {
-                    char msg[160];
-                    snprintf(msg, sizeof msg, "fit: no placement of a %ux%u source in %ux%u (a resampled side above 65535)", p->wins[i].w, p->wins[i].h, p->rs_w, p->rs_h);
-                    p->places[i] = jpgpu_placement{0, 0, 0, 0};
-                    throw DecodeError{JPGPU_ERR_FORMAT, msg};
-                }
-                // (a matrix the warp refuses fails the image alone, like a refused window)
-                if (p->warp_on && warps && !jpgpu::warp_check(warps[i].m, p->rs_w, p->rs_h)) {
-                    char msg[240];
-                    snprintf(msg, sizeof msg, "warp: matrix (%g, %g, %g, %g, %g, %g) refused for %ux%u (jpgpu_warp_check)", warps[i].m[0], warps[i].m[1], warps[i].m[2],
-                             warps[i].m[3], warps[i].m[4], warps[i].m[5], p->rs_w, p->rs_h);
-                    throw DecodeError{JPGPU_ERR_FORMAT, msg};
-                }
-                const char *bad = nullptr;  // (the format's means and stds against THIS image's channels)
-                if (p->tensor && !jpgpu::tensor_format_ok(p->tn.dtype, p->tn.reserved, p->tn.mean, p->tn.std, p->rgb ? 3u : d.ncomp, bad))
-                    throw DecodeError{JPGPU_ERR_FORMAT, std::string("tensor format: ") + bad};
-            }
-            if (device_entropy && p->infos[i].coding_process == JPGPU_CODING_DCT_PROGRESSIVE) {
-                // a progressive frame: its scans as tracks for the device (huff_prog_wave.hpp), if the stream is plainly eligible;
-                // how many of a call's eligible frames really go there is decided below, once all headers are read
-                if (device_progressive && fe.plan_progressive_scans(p->prog_plans[i])) {
-                    for (uint32_t c = 0; c < d.ncomp; c++) memcpy(cand[i].quantization_tables[c], fe.qtable_of_component(c), 128);
-                    p->has_frame[i] = 1;
-                    p->fes[i].reset();
-                } else if (device_progressive) {
-                    p->prog_plans[i].scans.clear();
-                    p->fes[i].reset(new Frontend(data[i], len[i], Frontend::Borrowed{}));
-                    read_info_with_options(p, *p->fes[i]);
-                }
-            } else if (device_entropy) {  // eligible for the device entropy decoder?  (the planning pass spends the object)
-                if (fe.plan_device_scans(p->plans[i])) {
-                    for (uint32_t c = 0; c < d.ncomp; c++) memcpy(cand[i].quantization_tables[c], fe.qtable_of_component(c), 128);
-                    // The plan holds all the device route needs: the front-end (45 kB of table space) goes back to the allocator of
-                    // this thread right away — 4,096 of them alive until the next call were 180 MB of fresh pages per call.
-                    p->has_frame[i] = 1;
-                    p->fes[i].reset();
-                } else {
-                    p->plans[i].clear();
-                    p->fes[i].reset(new Frontend(data[i], len[i], Frontend::Borrowed{}));
-                    read_info_with_options(p, *p->fes[i]);
-                }
-            }
-            if (p->fes[i]) p->has_frame[i] = p->fes[i]->has_frame() ? 1 : 0;
-            p->status[i] = JPGPU_OK;
-        } catch (const DecodeError &e) {
-            p->status[i] = e.code;
-            p->errors[i] = e.message;
-            if (p->fes[i]) p->has_frame[i] = p->fes[i]->has_frame() ? 1 : 0;
-        } catch (const std::exception &e) {
-            p->status[i] = JPGPU_ERR_INTERNAL;
-            p->errors[i] = e.what();
-        }
-    });
+// What the steps of one decode call share: the call's arguments and what an earlier step leaves for the later ones.
+struct Call {
+    jpgpu_pipeline *p;
+    const uint8_t *const *data;
+    const size_t *len;
+    const jpgpu_window *windows;  // the arguments of jpgpu_pipeline_decode_warped (NULL: none)
+    const uint8_t *flips;
+    const jpgpu_warp *warps;
+    uint32_t n, flags;
+    bool download, compact, device_entropy, device_progressive;
+    std::vector<jpgpu_image_desc> cand;  // per image: its descriptor, once its header is read
+    // Windows are checked per image as soon as its header gives the output grid, before anything is dealt to sub-batches — a batch refuses
+    // a bad window for all of its images, here only the image concerned fails.  win[i].w != 0 afterwards: image i runs the window kernel.
+    std::vector<jpgpu_window> win;
     bool any_window = false;
-    for (uint32_t i = 0; i < n && windows && !any_window; i++) any_window = p->status[i] == JPGPU_OK && win[i].w != 0;
-    if (device_entropy) keep_on_host_what_the_device_would_decode_slower(p, data, len, n);
-    const uint32_t n_prog_dev = device_progressive ? progressive_share_for_the_device(p, data, len, n) : 0u;
-    const double t1 = now_ms();
+    std::vector<uint32_t> ok;            // the images dealt to sub-batches, in the order dealt
+    std::vector<uint32_t> bounds{0u};    // sub-batch j = ok[bounds[j] .. bounds[j+1])
+    uint32_t n_prog_dev = 0;             // progressive frames the device decodes
+    uint32_t n_dev_subs = 0, first_prog_sub = 0;  // the first n_dev_subs sub-batches: entropy data for the device; from first_prog_sub on: progressive frames
+    double t0 = 0, t1 = 0, t2 = 0, t3 = 0, cpu0 = 0;
+    std::string prog_trace;              // JPGPU_PIPE_TRACE: step 3's line about progressive frames
+};
 
-    // 2. sub-batches of the images that have a frame (each kept while its geometry sequence repeats)
-    // Images bound for the device entropy decoder go first, in large sub-batches: one lane decodes one restart segment, a
-    // launch needs many images to fill the machine (and launches of different sub-batches were observed to run one
-    // after the other); host-decoded images follow in sub-batches of about 64 so that uploads, kernels and downloads overlap
-    // the remaining entropy decoding.
-    std::vector<uint32_t> ok;
+// throws what image i's decode() would throw
+static void decode_to_nothing(const Call &c, uint32_t i) {
+    Nothing nothing;
+    Frontend whole(c.data[i], c.len[i], Frontend::Borrowed{});
+    read_info_with_options(c.p, whole);
+    whole.decode_to(nothing);
+}
+
+// Step 1, per image on the pool: its header, its descriptor, and every check that fails the image alone.
+static void read_header(Call &c, uint32_t i) {
+    jpgpu_pipeline *p = c.p;
+    try {
+        p->fes[i].reset(new Frontend(c.data[i], c.len[i], Frontend::Borrowed{}));
+        Frontend &fe = *p->fes[i];
+        read_info_with_options(p, fe);
+        p->infos[i] = fe.info();
+        jpgpu_image_desc d;
+        memset(&d, 0, sizeof(d));
+        d.ncomp = fe.ncomp();
+        for (uint32_t k = 0; k < d.ncomp; k++) {
+            d.components[k] = fe.components()[k];
+            for (int q = 0; q < 64; q++) d.quantization_tables[k][q] = 1;  // set once the scans are parsed
+        }
+        d.out_w = fe.output_width(), d.out_h = fe.output_height(), d.color_transform = fe.color_transform();
+        // A block costs at least two bits.  A header that announces far more blocks than the file can hold (truncated or
+        // hostile: 65535 x 65535 in 200 bytes) would have the sub-batch allocate gigabytes of arenas and pinned staging
+        // — 2.5 s for one such file — before the entropy decoder finds out: let it find out first, into a sink that
+        // keeps nothing.  (A stream that decodes after all goes on as usual.)
+        uint64_t blocks = 0;
+        for (uint32_t k = 0; k < d.ncomp; k++) blocks += (uint64_t)d.components[k].block_width * d.components[k].block_height;
+        if ((uint64_t)c.len[i] * 8u < blocks * 2u) decode_to_nothing(c, i);
+        // what compute_image would refuse for this frame (an impossible sampling combination, a colour function whose row
+        // copy would overrun: src/decoder.rs:1300-1336, src/upsampler.rs:20-45) fails THIS image here — a sub-batch is
+        // created from frames the pixel backend takes, one refused frame must not fail its neighbours
+        jpgpu::ImageJob probe;
+        uint8_t *no_planes[4] = {nullptr, nullptr, nullptr, nullptr};
+        size_t out_len = 0;
+        std::string why;
+        int v = jpgpu::build_image_job(d.components, d.ncomp, no_planes, d.out_w, d.out_h, d.color_transform, nullptr, probe, out_len, why);
+        if (v != JPGPU_OK) {
+            decode_to_nothing(c, i);  // (the reference decodes the entropy data before it gets to compute_image: a stream that is broken as well reports that)
+            throw DecodeError{v, why};
+        }
+        c.cand[i] = d;
+        uint32_t gw = 0, gh = 0;
+        bool windowed = false;
+        v = jpgpu::batch_check_window(d, c.windows ? c.windows[i] : jpgpu_window{0, 0, 0, 0}, windowed, gw, gh, why);
+        if (v != JPGPU_OK) throw DecodeError{v, why};
+        p->wins[i] = jpgpu_window{0, 0, (uint16_t)gw, (uint16_t)gh};
+        if (windowed) c.win[i] = p->wins[i] = c.windows[i];
+        // (the output options against THIS image — planar output has no resample, the tensor format's means and stds are checked for
+        // its channels: the image fails alone, like a refused window)
+        v = jpgpu::output_image_rule(p->out, d.ncomp, probe.color_fn, why);
+        if (v != JPGPU_OK) throw DecodeError{v, why};
+        if (p->out.w) p->places[i] = jpgpu_placement{(uint16_t)p->out.w, (uint16_t)p->out.h, 0, 0};
+        // (a fit: the placement of THIS image's source — its window, else its output grid; a refused rule fails the image alone)
+        if (p->fit_on() && jpgpu_fit_placement(&p->fit, p->wins[i].w, p->wins[i].h, p->out.w, p->out.h, &p->places[i]) != JPGPU_OK) {
+            char msg[160];
+            snprintf(msg, sizeof msg, "fit: no placement of a %ux%u source in %ux%u (a resampled side above 65535)", p->wins[i].w, p->wins[i].h, p->out.w, p->out.h);
+            p->places[i] = jpgpu_placement{0, 0, 0, 0};
+            throw DecodeError{JPGPU_ERR_FORMAT, msg};
+        }
+        // (a matrix the warp refuses fails the image alone, like a refused window)
+        if (p->out.warp && c.warps && !jpgpu::warp_check(c.warps[i].m, p->out.w, p->out.h)) {
+            const double *m = c.warps[i].m;
+            char msg[240];
+            snprintf(msg, sizeof msg, "warp: matrix (%g, %g, %g, %g, %g, %g) refused for %ux%u (jpgpu_warp_check)", m[0], m[1], m[2], m[3], m[4], m[5], p->out.w, p->out.h);
+            throw DecodeError{JPGPU_ERR_FORMAT, msg};
+        }
+        // Eligible for the device?  A progressive frame: its scans as tracks (huff_prog_wave.hpp), if the stream is plainly eligible — how
+        // many of a call's eligible frames really go there is decided once all headers are read; any other: the device entropy decoder.
+        const bool prog = p->infos[i].coding_process == JPGPU_CODING_DCT_PROGRESSIVE;
+        if (c.device_entropy && (!prog || c.device_progressive)) {
+            if (prog ? fe.plan_progressive_scans(p->prog_plans[i]) : fe.plan_device_scans(p->plans[i])) {
+                for (uint32_t k = 0; k < d.ncomp; k++) memcpy(c.cand[i].quantization_tables[k], fe.qtable_of_component(k), 128);
+                // The plan holds all the device route needs: the front-end (45 kB of table space) goes back to the allocator of
+                // this thread right away — 4,096 of them alive until the next call were 180 MB of fresh pages per call.
+                p->has_frame[i] = 1;
+                p->fes[i].reset();
+            } else {  // (the planning pass spends the object: a fresh one for the host path)
+                p->prog_plans[i].scans.clear();
+                p->plans[i].clear();
+                p->fes[i].reset(new Frontend(c.data[i], c.len[i], Frontend::Borrowed{}));
+                read_info_with_options(p, *p->fes[i]);
+            }
+        }
+        if (p->fes[i]) p->has_frame[i] = p->fes[i]->has_frame() ? 1 : 0;
+        p->status[i] = JPGPU_OK;
+    } catch (const DecodeError &e) {
+        p->status[i] = e.code;
+        p->errors[i] = e.message;
+        if (p->fes[i]) p->has_frame[i] = p->fes[i]->has_frame() ? 1 : 0;
+    } catch (const std::exception &e) {
+        p->status[i] = JPGPU_ERR_INTERNAL;
+        p->errors[i] = e.what();
+    }
+}
+
+// Step 2a: the images that have a frame, in the order they are dealt, and where the sub-batches begin.
+// Images bound for the device entropy decoder go first, in large sub-batches: one lane decodes one restart segment, a
+// launch needs many images to fill the machine (and launches of different sub-batches were observed to run one
+// after the other); host-decoded images follow in sub-batches of about 64 so that uploads, kernels and downloads overlap
+// the remaining entropy decoding.
+static int deal_images(Call &c) {
+    jpgpu_pipeline *p = c.p;
+    const uint32_t n = c.n, n_prog_dev = c.n_prog_dev;
+    std::vector<uint32_t> &ok = c.ok, &bounds = c.bounds;
     for (uint32_t i = 0; i < n; i++)
         if (p->status[i] == JPGPU_OK && !p->plans[i].empty()) ok.push_back(i);
     const uint32_t n_dev = (uint32_t)ok.size();  // sequential streams for the chunk decoder; then the progressive frames for the track walker
@@ -854,197 +768,187 @@ int jpgpu_pipeline_decode_warped(jpgpu_pipeline *p, const uint8_t *const *data, 
     if ((uint32_t)ok.size() - n_dev != n_prog_dev) return jpgpu::set_err(p->err, JPGPU_ERR_INTERNAL, "pipeline: progressive dispatch count");
     for (uint32_t i = 0; i < n; i++)
         if (p->status[i] == JPGPU_OK && p->plans[i].empty() && p->prog_plans[i].scans.empty()) ok.push_back(i);
-    if (ok.empty()) {
-        p->t.headers_ms = t1 - t0;
-        p->t.total_ms = now_ms() - t0;
-        return JPGPU_OK;
-    }
-    std::vector<uint32_t> bounds{0u};  // sub-batch j = ok[bounds[j] .. bounds[j+1])
-    uint32_t n_dev_subs = 0;           // the first sub-batches hold the images whose entropy data goes to the device ...
-    uint32_t first_prog_sub = 0;       // ... of which those from this one on hold progressive frames (the track walker)
-    {
-        // one lane per chunk of a scan: 256 images fill the machine — but several sub-batches are in flight at a time (one compute
-        // stream each, and a hardware queue each when GPU_MAX_HW_QUEUES allows: jpgpu_process_init), the latency-bound late sync
-        // passes of one run next to the full passes of another, and staging, upload and kernels of neighbours overlap: 128 images
-        // per sub-batch, up to 32 of them (256 files per call 8.6 -> 7.5 ms, 1,024: 21.1 -> 18.8 ms, 4,096: 68.7 -> 63.5 ms against 256 x 16)
-        const long dev_sub_env = getenv("JPGPU_PIPE_DEV_SUB") ? atol(getenv("JPGPU_PIPE_DEV_SUB")) : 0;  // tuning knob (read per call)
-        // (round 4: calls of up to 512 files in sub-batches of 64 — four of them for 256 files: the first enters the device after a
-        // quarter of the staging, and four chains of latency-bound passes overlap instead of two; 256 files 6.5-7.1 -> 6.15 ms on the
-        // same boxes, 1,024 and 4,096 files unchanged: profiles/round4/08_sub_batch_sizes.txt)
-        const uint32_t dev_sub_images = dev_sub_env > 0 ? (uint32_t)dev_sub_env : (n_dev <= 512u ? kSubBatchImages : 2u * kSubBatchImages);
-        const long dev_cap_env = getenv("JPGPU_PIPE_MAX_DEV_SUBS") ? atol(getenv("JPGPU_PIPE_MAX_DEV_SUBS")) : 0;  // tuning knob (read per call)
-        const uint32_t dev_cap = dev_cap_env > 0 ? (uint32_t)std::min<long>(dev_cap_env, kMaxSubBatches / 2u) : kMaxSubBatches / 2u;
-        const uint32_t dev_subs = n_dev ? std::min<uint32_t>(dev_cap, (n_dev + dev_sub_images - 1u) / dev_sub_images) : 0u;
-        for (uint32_t j = 1; j <= dev_subs; j++) bounds.push_back((uint32_t)((uint64_t)n_dev * j / dev_subs));
-        // Progressive frames for the device: FEW, large sub-batches — a launch lasts as long as one lane's walk of the longest track
-        // whatever the number of frames (every track has a lane of its own while they fit the machine: 512 waves), so frames split
-        // over sub-batches that share a stream would pay that walk once per sub-batch; up to four, for the overlap of one's staging
-        // and upload with another's walk
-        const long prog_sub_env = getenv("JPGPU_PIPE_PROG_SUBS") ? atol(getenv("JPGPU_PIPE_PROG_SUBS")) : 0;  // tuning knob (read per call)
-        const uint32_t prog_subs = n_prog_dev ? std::min<uint32_t>({(uint32_t)(prog_sub_env > 0 ? prog_sub_env : 4), kMaxSubBatches / 2u - std::min(dev_subs, kMaxSubBatches / 2u - 1u),
-                                                                    (n_prog_dev + 255u) / 256u}) : 0u;
-        first_prog_sub = dev_subs;
-        for (uint32_t j = 1; j <= prog_subs; j++) bounds.push_back(n_dev + (uint32_t)((uint64_t)n_prog_dev * j / prog_subs));
-        n_dev_subs = dev_subs + prog_subs;
-        const uint32_t n_devs = n_dev + n_prog_dev, n_host = (uint32_t)ok.size() - n_devs;
-        const uint32_t host_subs = n_host ? std::min<uint32_t>(kMaxSubBatches - n_dev_subs, (n_host + kSubBatchImages - 1u) / kSubBatchImages) : 0u;
-        for (uint32_t j = 1; j <= host_subs; j++) bounds.push_back(n_devs + (uint32_t)((uint64_t)n_host * j / host_subs));
-    }
-    const uint32_t n_subs = (uint32_t)bounds.size() - 1u;
-    p->n_subs = n_subs;
-    for (uint32_t j = 0; j < n_subs; j++) {
-        SubBatch &sb = p->subs[j];
-        const uint32_t first = bounds[j], last = bounds[j + 1];
-        std::vector<jpgpu_image_desc> descs;
-        std::vector<jpgpu_window> wins;  // (stays empty when no image of the sub-batch has a window: jpgpu_batch_create's own path)
-        std::vector<uint8_t> fl;         // a tensor output: every image's flip
-        std::vector<jpgpu_placement> pls;  // a fit: every image's placement
-        std::vector<jpgpu_warp> wm;        // a warp: every image's matrix
-        bool sub_windowed = false;
-        for (uint32_t k = first; any_window && k < last; k++) sub_windowed = sub_windowed || win[ok[k]].w != 0;
-        for (uint32_t k = first; k < last; k++) {
-            p->sub_of[ok[k]] = (int32_t)j;
-            p->slot[ok[k]] = (int32_t)(k - first);
-            descs.push_back(cand[ok[k]]);
-            if (sub_windowed) wins.push_back(win[ok[k]]);
-            if (p->tensor) fl.push_back(flips && flips[ok[k]] ? 1 : 0);
-            if (p->fit_on) pls.push_back(p->places[ok[k]]);
-            if (p->warp_on) wm.push_back(warps ? warps[ok[k]] : jpgpu_warp{{1.0, 0.0, 0.0, 0.0, 1.0, 0.0}});
-        }
-        sb.remaining = last - first;
-        // Sub-batches of device-entropy images need no pinned staging for coefficients (their entropy-coded bytes are staged by
-        // the batch itself; an image the device decoder hands back is decoded into memory of its own): for 4096 x 1080p that
-        // would have been 28 GB of pinned host memory.
-        const bool staged = j >= n_dev_subs;
-        // (another output size: other tables, another output arena — the sub-batch is created anew)
-        bool reuse = sb.batch && descs.size() == sb.descs.size() && sb.compact == compact && (sb.h_coef != nullptr) == staged && sb.rs_w == p->rs_w && sb.rs_h == p->rs_h &&
-                     sb.rgb == p->rgb && sb.tensor == p->tensor && (!p->tensor || memcmp(&sb.tn, &p->tn, sizeof(jpgpu_tensor_format)) == 0);  // (... or another tensor format)
-        // (... or another fit: the batch is placed or not, and holds the fill, for its lifetime)
-        reuse = reuse && sb.filter == p->filter;  // (... or another filter: other tables throughout)
-        reuse = reuse && sb.fit_on == p->fit_on && (!p->fit_on || memcmp(&sb.fit, &p->fit, sizeof(jpgpu_fit)) == 0);
-        // (... or other warp options: the batch has a warp stage or not, and holds its filter and fill, for its lifetime)
-        reuse = reuse && sb.warp_on == p->warp_on && (!p->warp_on || memcmp(&sb.warp_opt, &p->warp_opt, sizeof(jpgpu_warp_options)) == 0);
-        const bool same_pls = pls.size() == sb.pls.size() && (pls.empty() || memcmp(pls.data(), sb.pls.data(), pls.size() * sizeof(jpgpu_placement)) == 0);
-        for (size_t k = 0; reuse && k < descs.size(); k++) reuse = same_geometry(descs[k], sb.descs[k]);
-        // ... and the same windows: the window group's geometry and the output offsets are made from them (a kept batch with other
-        // windows would return the pixels of the old ones).  Other windows for the SAME set of windowed images — a loader's fresh
-        // random crops — are set in place (jpgpu::batch_rewindow: the arenas, plans and staging blocks stay; JPGPU_PIPE_REWINDOW=0, read
-        // per call: A/B); anything else is a new batch.
-        const double s0 = getenv("JPGPU_PIPE_TRACE") ? now_ms() : 0.0;
-        const char *how = reuse ? "kept" : "created";
-        if (reuse && !(wins.size() == sb.wins.size() && (wins.empty() || memcmp(wins.data(), sb.wins.data(), wins.size() * sizeof(jpgpu_window)) == 0))) {
-            const char *rw = getenv("JPGPU_PIPE_REWINDOW");
-            int rrc = JPGPU_ERR_UNSUPPORTED;
-            if (!wins.empty() && !sb.wins.empty() && !(rw && atoi(rw) == 0)) rrc = jpgpu::batch_rewindow(sb.batch, wins.data(), pls.empty() ? nullptr : pls.data());
-            if (rrc == JPGPU_OK) sb.wins = wins, sb.pls = pls, how = "re-windowed in place";  // (fresh windows at the same fit: re-placed with them)
-            else reuse = false, how = "created (other windows)";
-        } else if (reuse && !same_pls) {
-            reuse = false, how = "created (other placements)";
-        }
-        if (!reuse) {
-            sb.drop();
-            const uint32_t bf = (p->rgb ? JPGPU_BATCH_RGB_OUTPUT : JPGPU_BATCH_DEFAULT) |  // (every image three channels: the batch's resample converts)
-                                JPGPU_BATCH_FILTER(p->filter);                             // (0 without an output size: checked above)
-            rc = p->warp_on ? jpgpu_batch_create_warped(p->device, descs.data(), wins.empty() ? nullptr : wins.data(), p->fit_on ? pls.data() : nullptr, p->fit.fill, p->rs_w,
-                                                        p->rs_h, p->tensor ? &p->tn : nullptr, &p->warp_opt, (uint32_t)descs.size(), bf, &sb.batch)
-                 : p->fit_on ? jpgpu_batch_create_placed(p->device, descs.data(), wins.empty() ? nullptr : wins.data(), pls.data(), p->fit.fill, p->rs_w, p->rs_h,
-                                                       p->tensor ? &p->tn : nullptr, (uint32_t)descs.size(), bf, &sb.batch)
-                 : p->tensor ? jpgpu_batch_create_tensor(p->device, descs.data(), wins.empty() ? nullptr : wins.data(), p->rs_w, p->rs_h, &p->tn, (uint32_t)descs.size(), bf, &sb.batch)
-                 : p->rs_w ? jpgpu_batch_create_resized(p->device, descs.data(), wins.empty() ? nullptr : wins.data(), p->rs_w, p->rs_h, (uint32_t)descs.size(), bf, &sb.batch)
-                         : jpgpu_batch_create_windowed(p->device, descs.data(), wins.empty() ? nullptr : wins.data(), (uint32_t)descs.size(), JPGPU_BATCH_DEFAULT, &sb.batch);
-            if (rc) {
-                // a frame the pixel backend refuses (e.g. an impossible sampling combination) fails the images of
-                // its sub-batch the way the reference fails it in compute_image
-                const std::string msg = sb.batch ? jpgpu_batch_last_error(sb.batch) : "batch_create";
-                for (uint32_t k = first; k < last; k++) {
-                    p->status[ok[k]] = rc;
-                    p->errors[ok[k]] = msg;
-                    p->sub_of[ok[k]] = p->slot[ok[k]] = -1;
-                }
-                sb.drop();
-                sb.remaining = 0;
-                continue;
-            }
-            sb.descs = descs;
-            sb.wins = wins;
-            sb.rs_w = p->rs_w, sb.rs_h = p->rs_h;
-            sb.tensor = p->tensor, sb.tn = p->tn;
-            sb.rgb = p->rgb;
-            sb.filter = p->filter;
-            sb.fit_on = p->fit_on, sb.fit = p->fit, sb.pls = pls;
-            sb.flips.assign(descs.size(), 0);
-            sb.warp_on = p->warp_on, sb.warp_opt = p->warp_opt;
-            sb.warps.assign(p->warp_on ? descs.size() : 0, jpgpu_warp{{1.0, 0.0, 0.0, 0.0, 1.0, 0.0}});
-            sb.compact = compact;
-            sb.h_coef_bytes = jpgpu_batch_coef_arena_bytes(sb.batch);
-            if (compact) {  // worst-case compact size per component (12 B/block more than dense), 256-B aligned
-                sb.stage_off.assign(descs.size() * 4, 0);
-                size_t so = 0;
-                for (size_t k = 0; k < descs.size(); k++)
-                    for (uint32_t c = 0; c < descs[k].ncomp; c++) {
-                        sb.stage_off[k * 4 + c] = so;
-                        so += jpgpu::align_up(jpgpu::compact_max_bytes(jpgpu_batch_coef_bytes(sb.batch, (uint32_t)k, c) / 128), 256);
-                    }
-                sb.h_coef_bytes = std::max<size_t>(so, 256);
-            }
-            if (staged) P_HIP(hipHostMalloc((void **)&sb.h_coef, sb.h_coef_bytes, hipHostMallocDefault));
-            else sb.h_coef_bytes = 0;
-        }
-        if (p->tensor && fl != sb.flips) {  // (other flips, kept or new: set in place — a field of the job records, no size or offset changes)
-            rc = jpgpu_batch_set_flips(sb.batch, fl.data());
-            if (rc) return jpgpu::set_err(p->err, rc, "%s", jpgpu_batch_last_error(sb.batch));
-            sb.flips = fl;
-        }
-        // (other matrices, kept or new: set in place like the flips — fields of the job records)
-        if (p->warp_on && memcmp(wm.data(), sb.warps.data(), wm.size() * sizeof(jpgpu_warp)) != 0) {
-            rc = jpgpu_batch_set_warps(sb.batch, wm.data());
-            if (rc) return jpgpu::set_err(p->err, rc, "%s", jpgpu_batch_last_error(sb.batch));
-            sb.warps = wm;
-        }
-        if (download && (!sb.h_out || sb.h_out_bytes < jpgpu_batch_out_arena_bytes(sb.batch))) {
-            if (sb.h_out) (void)hipHostFree(sb.h_out);
-            sb.h_out = nullptr;
-            // (a sub-batch with windows: a quarter more than these windows need, at most what the whole images take — the totals of a
-            // loader's fresh random crops differ little from call to call, and pinning memory anew costs milliseconds)
-            const size_t need = jpgpu_batch_out_arena_bytes(sb.batch);
-            sb.h_out_bytes = sb.wins.empty() ? need : jpgpu::arena_headroom(need, jpgpu::batch_out_arena_bound(sb.batch));
-            P_HIP(hipHostMalloc((void **)&sb.h_out, sb.h_out_bytes, hipHostMallocDefault));
-        }
-        if (s0 != 0.0) fprintf(stderr, "pipeline trace: sub-batch %u (%zu images, %zu with a window): %s in %.2f ms\n", j, descs.size(), (size_t)jpgpu::batch_windowed_images(sb.batch), how, now_ms() - s0);
-        const char *pth = jpgpu_batch_path(sb.batch);
-        if (p->path.empty()) p->path = pth;
-        else if (p->path != pth) p->path = "mixed";
-    }
-    p->gather_bytes = 0;
-    if (p->gather_on) {  // (a child of a multi-device pipeline: where its sub-batches' pixels go on the gathering device)
-        size_t total = 0;
-        p->gather_off.assign(n_subs, 0);
-        for (uint32_t j = 0; j < n_subs; j++) {
-            p->gather_off[j] = total;
-            total += p->subs[j].batch ? jpgpu::align_up(jpgpu_batch_out_arena_bytes(p->subs[j].batch), 256) : 0;
-        }
-        if (total > p->gather_cap) {
-            // (allocated on the gathering device by this child's thread: hipSetDevice is per thread)
-            if (hipSetDevice(p->gather_device) != hipSuccess) return jpgpu::set_err(p->err, JPGPU_ERR_IO, "gather: cannot select device %d", p->gather_device);
-            if (p->d_gather) (void)hipFree(p->d_gather);
-            p->d_gather = nullptr;
-            p->gather_cap = 0;
-            const hipError_t ge = hipMalloc((void **)&p->d_gather, total + total / 8);
-            (void)hipSetDevice(p->device);
-            if (ge != hipSuccess) return jpgpu::set_err(p->err, JPGPU_ERR_IO, "gather: %zu bytes on device %d: %s", total + total / 8, p->gather_device, hipGetErrorString(ge));
-            p->gather_cap = total + total / 8;
-        }
-        if (!p->gather_stream) P_HIP(hipStreamCreateWithFlags(&p->gather_stream, hipStreamNonBlocking));  // on THIS device: the source drives the copy
-        while (p->gather_ev.size() < n_subs) {
-            hipEvent_t a = nullptr, b = nullptr;
-            P_HIP(hipEventCreate(&a));
-            P_HIP(hipEventCreate(&b));
-            p->gather_ev.emplace_back(a, b);
-        }
-    }
-    const double t2 = now_ms();
+    if (ok.empty()) return JPGPU_OK;
+    // one lane per chunk of a scan: 256 images fill the machine — but several sub-batches are in flight at a time (one compute
+    // stream each, and a hardware queue each when GPU_MAX_HW_QUEUES allows: jpgpu_process_init), the latency-bound late sync
+    // passes of one run next to the full passes of another, and staging, upload and kernels of neighbours overlap: 128 images
+    // per sub-batch, up to 32 of them (256 files per call 8.6 -> 7.5 ms, 1,024: 21.1 -> 18.8 ms, 4,096: 68.7 -> 63.5 ms against 256 x 16)
+    const long dev_sub_env = getenv("JPGPU_PIPE_DEV_SUB") ? atol(getenv("JPGPU_PIPE_DEV_SUB")) : 0;  // tuning knob (read per call)
+    // (round 4: calls of up to 512 files in sub-batches of 64 — four of them for 256 files: the first enters the device after a
+    // quarter of the staging, and four chains of latency-bound passes overlap instead of two; 256 files 6.5-7.1 -> 6.15 ms on the
+    // same boxes, 1,024 and 4,096 files unchanged: profiles/round4/08_sub_batch_sizes.txt)
+    const uint32_t dev_sub_images = dev_sub_env > 0 ? (uint32_t)dev_sub_env : (n_dev <= 512u ? kSubBatchImages : 2u * kSubBatchImages);
+    const long dev_cap_env = getenv("JPGPU_PIPE_MAX_DEV_SUBS") ? atol(getenv("JPGPU_PIPE_MAX_DEV_SUBS")) : 0;  // tuning knob (read per call)
+    const uint32_t dev_cap = dev_cap_env > 0 ? (uint32_t)std::min<long>(dev_cap_env, kMaxSubBatches / 2u) : kMaxSubBatches / 2u;
+    const uint32_t dev_subs = n_dev ? std::min<uint32_t>(dev_cap, (n_dev + dev_sub_images - 1u) / dev_sub_images) : 0u;
+    for (uint32_t j = 1; j <= dev_subs; j++) bounds.push_back((uint32_t)((uint64_t)n_dev * j / dev_subs));
+    // Progressive frames for the device: FEW, large sub-batches — a launch lasts as long as one lane's walk of the longest track
+    // whatever the number of frames (every track has a lane of its own while they fit the machine: 512 waves), so frames split
+    // over sub-batches that share a stream would pay that walk once per sub-batch; up to four, for the overlap of one's staging
+    // and upload with another's walk
+    const long prog_sub_env = getenv("JPGPU_PIPE_PROG_SUBS") ? atol(getenv("JPGPU_PIPE_PROG_SUBS")) : 0;  // tuning knob (read per call)
+    const uint32_t prog_subs = n_prog_dev ? std::min<uint32_t>({(uint32_t)(prog_sub_env > 0 ? prog_sub_env : 4), kMaxSubBatches / 2u - std::min(dev_subs, kMaxSubBatches / 2u - 1u),
+                                                                (n_prog_dev + 255u) / 256u}) : 0u;
+    c.first_prog_sub = dev_subs;
+    for (uint32_t j = 1; j <= prog_subs; j++) bounds.push_back(n_dev + (uint32_t)((uint64_t)n_prog_dev * j / prog_subs));
+    c.n_dev_subs = dev_subs + prog_subs;
+    const uint32_t n_devs = n_dev + n_prog_dev, n_host = (uint32_t)ok.size() - n_devs;
+    const uint32_t host_subs = n_host ? std::min<uint32_t>(kMaxSubBatches - c.n_dev_subs, (n_host + kSubBatchImages - 1u) / kSubBatchImages) : 0u;
+    for (uint32_t j = 1; j <= host_subs; j++) bounds.push_back(n_devs + (uint32_t)((uint64_t)n_host * j / host_subs));
+    return JPGPU_OK;
+}
 
-    // 3. entropy decoding (pool) + per-image upload and per-sub-batch kernels / download (one uploader thread)
+// Step 2b: sub-batch j of the call — kept while its geometry sequence and the output options repeat, given other windows in place,
+// or created; then this call's flips and matrices, and pinned memory for its pixels.
+static int prepare_sub_batch(Call &c, uint32_t j) {
+    jpgpu_pipeline *p = c.p;
+    const std::vector<uint32_t> &ok = c.ok;
+    SubBatch &sb = p->subs[j];
+    const uint32_t first = c.bounds[j], last = c.bounds[j + 1];
+    std::vector<jpgpu_image_desc> descs;
+    std::vector<jpgpu_window> wins;  // (stays empty when no image of the sub-batch has a window: jpgpu_batch_create's own path)
+    std::vector<uint8_t> fl;         // a tensor output: every image's flip
+    std::vector<jpgpu_placement> pls;  // a fit: every image's placement
+    std::vector<jpgpu_warp> wm;        // a warp: every image's matrix
+    bool sub_windowed = false;
+    for (uint32_t k = first; c.any_window && k < last; k++) sub_windowed = sub_windowed || c.win[ok[k]].w != 0;
+    for (uint32_t k = first; k < last; k++) {
+        p->sub_of[ok[k]] = (int32_t)j;
+        p->slot[ok[k]] = (int32_t)(k - first);
+        descs.push_back(c.cand[ok[k]]);
+        if (sub_windowed) wins.push_back(c.win[ok[k]]);
+        if (p->out.tensor) fl.push_back(c.flips && c.flips[ok[k]] ? 1 : 0);
+        if (p->fit_on()) pls.push_back(p->places[ok[k]]);
+        if (p->out.warp) wm.push_back(c.warps ? c.warps[ok[k]] : jpgpu_warp{{1.0, 0.0, 0.0, 0.0, 1.0, 0.0}});
+    }
+    sb.remaining = last - first;
+    // Sub-batches of device-entropy images need no pinned staging for coefficients (their entropy-coded bytes are staged by
+    // the batch itself; an image the device decoder hands back is decoded into memory of its own): for 4096 x 1080p that
+    // would have been 28 GB of pinned host memory.
+    const bool staged = j >= c.n_dev_subs;
+    // (other output options — another size, format, filter, fill or warp stage — or another fit rule: other tables, arenas and
+    // launches for the batch's lifetime, the sub-batch is created anew)
+    bool reuse = sb.batch && descs.size() == sb.descs.size() && sb.compact == c.compact && (sb.h_coef != nullptr) == staged && sb.made_with == p->out &&
+                 sb.fit.mode == p->fit.mode && sb.fit.size == p->fit.size;
+    const bool same_pls = pls.size() == sb.pls.size() && (pls.empty() || memcmp(pls.data(), sb.pls.data(), pls.size() * sizeof(jpgpu_placement)) == 0);
+    for (size_t k = 0; reuse && k < descs.size(); k++) reuse = same_geometry(descs[k], sb.descs[k]);
+    // ... and the same windows: the window group's geometry and the output offsets are made from them (a kept batch with other
+    // windows would return the pixels of the old ones).  Other windows for the SAME set of windowed images — a loader's fresh
+    // random crops — are set in place (jpgpu::batch_rewindow: the arenas, plans and staging blocks stay; JPGPU_PIPE_REWINDOW=0, read
+    // per call: A/B); anything else is a new batch.
+    const double s0 = getenv("JPGPU_PIPE_TRACE") ? now_ms() : 0.0;
+    const char *how = reuse ? "kept" : "created";
+    if (reuse && !(wins.size() == sb.wins.size() && (wins.empty() || memcmp(wins.data(), sb.wins.data(), wins.size() * sizeof(jpgpu_window)) == 0))) {
+        const char *rw = getenv("JPGPU_PIPE_REWINDOW");
+        int rrc = JPGPU_ERR_UNSUPPORTED;
+        if (!wins.empty() && !sb.wins.empty() && !(rw && atoi(rw) == 0)) rrc = jpgpu::batch_rewindow(sb.batch, wins.data(), pls.empty() ? nullptr : pls.data());
+        if (rrc == JPGPU_OK) sb.wins = wins, sb.pls = pls, how = "re-windowed in place";  // (fresh windows at the same fit: re-placed with them)
+        else reuse = false, how = "created (other windows)";
+    } else if (reuse && !same_pls) {
+        reuse = false, how = "created (other placements)";
+    }
+    int rc = JPGPU_OK;
+    if (!reuse) {
+        sb.drop();
+        rc = jpgpu::batch_create_with(p->device, descs.data(), wins.empty() ? nullptr : wins.data(), p->fit_on() ? pls.data() : nullptr, (uint32_t)descs.size(), p->out, &sb.batch);
+        if (rc) {
+            // a frame the pixel backend refuses (e.g. an impossible sampling combination) fails the images of
+            // its sub-batch the way the reference fails it in compute_image
+            const std::string msg = sb.batch ? jpgpu_batch_last_error(sb.batch) : "batch_create";
+            for (uint32_t k = first; k < last; k++) {
+                p->status[ok[k]] = rc;
+                p->errors[ok[k]] = msg;
+                p->sub_of[ok[k]] = p->slot[ok[k]] = -1;
+            }
+            sb.drop();
+            sb.remaining = 0;
+            return JPGPU_OK;
+        }
+        sb.descs = descs;
+        sb.wins = wins;
+        sb.made_with = p->out, sb.fit = p->fit, sb.pls = pls;
+        sb.flips.assign(descs.size(), 0);
+        sb.warps.assign(p->out.warp ? descs.size() : 0, jpgpu_warp{{1.0, 0.0, 0.0, 0.0, 1.0, 0.0}});
+        sb.compact = c.compact;
+        sb.h_coef_bytes = jpgpu_batch_coef_arena_bytes(sb.batch);
+        if (c.compact) {  // worst-case compact size per component (12 B/block more than dense), 256-B aligned
+            sb.stage_off.assign(descs.size() * 4, 0);
+            size_t so = 0;
+            for (size_t k = 0; k < descs.size(); k++)
+                for (uint32_t cc = 0; cc < descs[k].ncomp; cc++) {
+                    sb.stage_off[k * 4 + cc] = so;
+                    so += jpgpu::align_up(jpgpu::compact_max_bytes(jpgpu_batch_coef_bytes(sb.batch, (uint32_t)k, cc) / 128), 256);
+                }
+            sb.h_coef_bytes = std::max<size_t>(so, 256);
+        }
+        if (staged) P_HIP(hipHostMalloc((void **)&sb.h_coef, sb.h_coef_bytes, hipHostMallocDefault));
+        else sb.h_coef_bytes = 0;
+    }
+    if (p->out.tensor && fl != sb.flips) {  // (other flips, kept or new: set in place — a field of the job records, no size or offset changes)
+        rc = jpgpu_batch_set_flips(sb.batch, fl.data());
+        if (rc) return jpgpu::set_err(p->err, rc, "%s", jpgpu_batch_last_error(sb.batch));
+        sb.flips = fl;
+    }
+    // (other matrices, kept or new: set in place like the flips — fields of the job records)
+    if (p->out.warp && memcmp(wm.data(), sb.warps.data(), wm.size() * sizeof(jpgpu_warp)) != 0) {
+        rc = jpgpu_batch_set_warps(sb.batch, wm.data());
+        if (rc) return jpgpu::set_err(p->err, rc, "%s", jpgpu_batch_last_error(sb.batch));
+        sb.warps = wm;
+    }
+    if (c.download && (!sb.h_out || sb.h_out_bytes < jpgpu_batch_out_arena_bytes(sb.batch))) {
+        if (sb.h_out) (void)hipHostFree(sb.h_out);
+        sb.h_out = nullptr;
+        // (a sub-batch with windows: a quarter more than these windows need, at most what the whole images take — the totals of a
+        // loader's fresh random crops differ little from call to call, and pinning memory anew costs milliseconds)
+        const size_t need = jpgpu_batch_out_arena_bytes(sb.batch);
+        sb.h_out_bytes = sb.wins.empty() ? need : jpgpu::arena_headroom(need, jpgpu::batch_out_arena_bound(sb.batch));
+        P_HIP(hipHostMalloc((void **)&sb.h_out, sb.h_out_bytes, hipHostMallocDefault));
+    }
+    if (s0 != 0.0) fprintf(stderr, "pipeline trace: sub-batch %u (%zu images, %zu with a window): %s in %.2f ms\n", j, descs.size(), (size_t)jpgpu::batch_windowed_images(sb.batch), how, now_ms() - s0);
+    const char *pth = jpgpu_batch_path(sb.batch);
+    if (p->path.empty()) p->path = pth;
+    else if (p->path != pth) p->path = "mixed";
+    return JPGPU_OK;
+}
+
+// Step 2c, a child of a multi-device pipeline: where its sub-batches' pixels go on the gathering device, the stream and the events.
+static int setup_gather(jpgpu_pipeline *p, uint32_t n_subs) {
+    size_t total = 0;
+    p->gather_off.assign(n_subs, 0);
+    for (uint32_t j = 0; j < n_subs; j++) {
+        p->gather_off[j] = total;
+        total += p->subs[j].batch ? jpgpu::align_up(jpgpu_batch_out_arena_bytes(p->subs[j].batch), 256) : 0;
+    }
+    if (total > p->gather_cap) {
+        // (allocated on the gathering device by this child's thread: hipSetDevice is per thread)
+        if (hipSetDevice(p->gather_device) != hipSuccess) return jpgpu::set_err(p->err, JPGPU_ERR_IO, "gather: cannot select device %d", p->gather_device);
+        if (p->d_gather) (void)hipFree(p->d_gather);
+        p->d_gather = nullptr;
+        p->gather_cap = 0;
+        const hipError_t ge = hipMalloc((void **)&p->d_gather, total + total / 8);
+        (void)hipSetDevice(p->device);
+        if (ge != hipSuccess) return jpgpu::set_err(p->err, JPGPU_ERR_IO, "gather: %zu bytes on device %d: %s", total + total / 8, p->gather_device, hipGetErrorString(ge));
+        p->gather_cap = total + total / 8;
+    }
+    if (!p->gather_stream) P_HIP(hipStreamCreateWithFlags(&p->gather_stream, hipStreamNonBlocking));  // on THIS device: the source drives the copy
+    while (p->gather_ev.size() < n_subs) {
+        hipEvent_t a = nullptr, b = nullptr;
+        P_HIP(hipEventCreate(&a));
+        P_HIP(hipEventCreate(&b));
+        p->gather_ev.emplace_back(a, b);
+    }
+    return JPGPU_OK;
+}
+
+// Step 3: entropy decoding (pool) + per-image upload and per-sub-batch kernels / download (one uploader thread)
+static int decode_upload_and_launch(Call &c) {
+    jpgpu_pipeline *p = c.p;
+    const uint8_t *const *data = c.data;
+    const size_t *len = c.len;
+    const uint32_t n = c.n, flags = c.flags, n_dev_subs = c.n_dev_subs, first_prog_sub = c.first_prog_sub;
+    const bool download = c.download, device_entropy = c.device_entropy;
+    const std::vector<jpgpu_image_desc> &cand = c.cand;
+    const double t2 = c.t2;
     std::atomic<uint64_t> jpeg_bytes{0}, coef_bytes{0};
     std::atomic<int> hip_failed{0};
     UploadQueue q;
@@ -1055,12 +959,11 @@ int jpgpu_pipeline_decode_warped(jpgpu_pipeline *p, const uint8_t *const *data, 
     std::vector<size_t> cbytes((size_t)n * 4, 0);  // compact mode: bytes per component
     std::vector<int> crange((size_t)n * 4, 0);
     std::string launch_err;
-    double t_last_upload = t2;
     const bool trace = getenv("JPGPU_PIPE_TRACE") != nullptr;
     std::mutex trace_m;
     double busy_sum = 0, busy_max = 0, last_end = 0, prog_host_ms = 0, prog_dev_ms = 0;
-    uint64_t prog_host_bytes = 0, prog_dev_bytes = 0;
-    uint32_t device_prog_images = 0, prog_host_images = 0, n_host_images = 0, light_images = 0, entry_images = 0;
+    uint64_t prog_host_bytes = 0;
+    uint32_t device_prog_images = 0, prog_host_images = 0, light_images = 0, entry_images = 0;
     // Host light (include/jpgpu_decoder.h) is the DEFAULT at every thread count (round 6); JPGPU_PIPELINE_HOST_STAGED asks for the host's
     // staging pass.  Why no rule by thread count any more (round 5 chose staging above 16 worker threads): host staging swings 2 x with the
     // box and with what else runs on it — 4,096 x 1080p at 16 CPUs / 32 threads: 49-51 ms on quiet boxes, 60.7 ms on the driver's, 115-119 ms
@@ -1090,13 +993,11 @@ int jpgpu_pipeline_decode_warped(jpgpu_pipeline *p, const uint8_t *const *data, 
     double dev_ms[4] = {0, 0, 0, 0};  // JPGPU_BATCH_KERNEL_TIMES: phases of the device entropy path, summed over the sub-batches
     bool dev_ms_valid = false;
     // the pool is idle while device-entropy images are staged (its tasks for them return at once): lend it to the copy
-    std::mutex par_m;
     // (a team of its own, kept between calls: the pool proper may still be inside its run() of step 3 when the uploader thread gets
     // here, and sixteen fresh threads per launch — 512 thread starts per 4,096-file call — were half of a launch's host time)
     const std::function<void(uint32_t, const std::function<void(uint32_t)> &)> par_for = [&](uint32_t cnt, const std::function<void(uint32_t)> &fn) {
         p->stage_pool->run(cnt, fn);
     };
-    (void)par_m;
     // What follows the pixel kernels of sub-batch `sj` on its compute stream `cs`: the download to pinned host memory and / or the
     // copy to the gathering device, each on a stream of its own behind the `decoded` event (the compute stream goes on with the next
     // sub-batch that shares it).  Called again when a sub-batch is decoded a second time (an image the device decoder handed back).
@@ -1191,10 +1092,7 @@ int jpgpu_pipeline_decode_warped(jpgpu_pipeline *p, const uint8_t *const *data, 
                         const double l0 = now_ms();
                         if ((uint32_t)p->sub_of[i] >= first_prog_sub) {  // progressive frames: one lane per track (huff_prog_wave.hpp)
                             std::vector<jpgpu::DeviceProgressiveImage> list;
-                            for (uint32_t di : dv) {
-                                list.push_back(jpgpu::DeviceProgressiveImage{(uint32_t)p->slot[di], data[di], &p->prog_plans[di]});
-                                prog_dev_bytes += len[di];
-                            }
+                            for (uint32_t di : dv) list.push_back(jpgpu::DeviceProgressiveImage{(uint32_t)p->slot[di], data[di], &p->prog_plans[di]});
                             device_prog_images += (uint32_t)dv.size();
                             okk = jpgpu::batch_device_progressive_launch(sb.batch, list.data(), (uint32_t)list.size(), cs, &par_for,
                                                                          p->copy_streams[(uint32_t)p->sub_of[i] % kCopyStreams],
@@ -1303,7 +1201,6 @@ int jpgpu_pipeline_decode_warped(jpgpu_pipeline *p, const uint8_t *const *data, 
                 pending_subs.clear();
             }
         }
-        t_last_upload = now_ms();
     });
     p->pool->run(n, [&](uint32_t i) {
         if (p->status[i] != JPGPU_OK) return;
@@ -1334,7 +1231,6 @@ int jpgpu_pipeline_decode_warped(jpgpu_pipeline *p, const uint8_t *const *data, 
                 busy_sum += w1 - w0;
                 busy_max = std::max(busy_max, w1 - w0);
                 last_end = std::max(last_end, w1);
-                n_host_images++;
                 if (p->infos[i].coding_process == JPGPU_CODING_DCT_PROGRESSIVE) {
                     prog_host_ms += w1 - w0;
                     prog_host_bytes += len[i];
@@ -1374,57 +1270,129 @@ int jpgpu_pipeline_decode_warped(jpgpu_pipeline *p, const uint8_t *const *data, 
     if (hip_failed.load())
         return jpgpu::set_err(p->err, JPGPU_ERR_IO, "pipeline: upload / launch failed%s%s", launch_err.empty() ? "" : ": ", launch_err.c_str());
 
-    // 4. drain: whatever kernels and downloads are still in flight
-    for (uint32_t k = 0; k < kCopyStreams; k++) P_HIP(hipStreamSynchronize(p->copy_streams[k]));
-    for (uint32_t k = 0; k < p->n_compute; k++) P_HIP(hipStreamSynchronize(p->compute[k]));
-    if (trace) fprintf(stderr, "pipeline trace: copy and compute streams drained at +%.2f ms\n", now_ms() - t2);
-    if (download)
-        for (uint32_t k = 0; k < kD2HStreams; k++) {
-            P_HIP(hipStreamSynchronize(p->d2h[k]));
-            if (trace) fprintf(stderr, "pipeline trace: download stream %u drained at +%.2f ms\n", k, now_ms() - t2);
-        }
-    // (a child's gather stream is NOT waited for here: the parent does, after every child has decoded — what it then still waits is the exposed part)
-    const double t4 = now_ms();
-    uint64_t pixel_bytes = 0;
-    uint32_t okc = 0, windowed_images = 0;
-    for (uint32_t i = 0; i < n; i++)
-        if (p->status[i] == JPGPU_OK) {
-            okc++;
-            if (any_window && jpgpu::batch_image_windowed(p->subs[(uint32_t)p->sub_of[i]].batch, (uint32_t)p->slot[i])) windowed_images++;
-            pixel_bytes += jpgpu_batch_out_bytes(p->subs[(uint32_t)p->sub_of[i]].batch, (uint32_t)p->slot[i]);
-        }
-    p->t.headers_ms = t1 - t0;
-    p->t.setup_ms = t2 - t1;
-    p->t.entropy_and_upload_ms = t3 - t2;
-    p->t.kernels_ms = 0.0;  // overlapped: see drain_ms
-    p->t.download_ms = t4 - t3;
-    p->t.total_ms = t4 - t0;
-    p->t.decode_ms = t4 - t0;
-    p->t.images_ok = okc;
+    // what the timings (jpgpu_pipeline_last_timings) take from this step; the rest: finish_timings
+    c.t3 = t3;
     p->t.dev_times_valid = dev_ms_valid ? 1u : 0u;
-    p->t.dev_fill_ms = dev_ms[0];
-    p->t.dev_sync_ms = dev_ms[1];
-    p->t.dev_write_ms = dev_ms[2];
-    p->t.dev_pixel_ms = dev_ms[3];
-    p->t.jpeg_bytes = jpeg_bytes.load();
-    p->t.coefficient_bytes = coef_bytes.load();
-    p->t.pixel_bytes = pixel_bytes;
-    p->t.images_device_entropy = device_images;
-    p->t.images_device_rejected = device_rejected;
-    p->t.images_device_progressive = device_prog_images;
-    p->t.images_host_light = light_images;
-    p->t.images_entry_pixels = entry_images;
-    p->t.images_windowed = windowed_images;
-    p->t.images_resized = p->rs_w ? okc : 0u;
-    p->t.input_pinned = input_pinned ? 1u : 0u;
-    if (trace && (prog_host_bytes || device_prog_images))
-        fprintf(stderr, "pipeline trace: progressive frames: %u on the device (walk %.2f ms, launches + range scan + pixels %.2f ms), %u on the host (entropy phase %.2f ms, %.1f ns per byte and thread)\n",
-                device_prog_images, prog_dev_ms, prog_dev_extra_ms, prog_host_images, t3 - t2, prog_host_bytes ? prog_host_ms * 1e6 / (double)prog_host_bytes : 0.0);
-    p->t.cpu_ms = process_cpu_ms() - cpu0;
-    (void)t_last_upload;
+    p->t.dev_fill_ms = dev_ms[0], p->t.dev_sync_ms = dev_ms[1], p->t.dev_write_ms = dev_ms[2], p->t.dev_pixel_ms = dev_ms[3];
+    p->t.jpeg_bytes = jpeg_bytes.load(), p->t.coefficient_bytes = coef_bytes.load();
+    p->t.images_device_entropy = device_images, p->t.images_device_rejected = device_rejected, p->t.images_device_progressive = device_prog_images;
+    p->t.images_host_light = light_images, p->t.images_entry_pixels = entry_images, p->t.input_pinned = input_pinned ? 1u : 0u;
+    if (trace && (prog_host_bytes || device_prog_images)) {  // (printed behind the drain's lines)
+        char line[400];
+        snprintf(line, sizeof line, "pipeline trace: progressive frames: %u on the device (walk %.2f ms, launches + range scan + pixels %.2f ms), %u on the host (entropy phase %.2f ms, %.1f ns per byte and thread)\n",
+                 device_prog_images, prog_dev_ms, prog_dev_extra_ms, prog_host_images, t3 - t2, prog_host_bytes ? prog_host_ms * 1e6 / (double)prog_host_bytes : 0.0);
+        c.prog_trace = line;
+    }
     return JPGPU_OK;
 }
 
+// The rest of the call's timings, once the drain is over
+static void finish_timings(Call &c) {
+    jpgpu_pipeline *p = c.p;
+    const double t4 = now_ms();
+    uint64_t pixel_bytes = 0;
+    uint32_t okc = 0, windowed_images = 0;
+    for (uint32_t i = 0; i < c.n; i++)
+        if (p->status[i] == JPGPU_OK) {
+            okc++;
+            if (c.any_window && jpgpu::batch_image_windowed(p->subs[(uint32_t)p->sub_of[i]].batch, (uint32_t)p->slot[i])) windowed_images++;
+            pixel_bytes += jpgpu_batch_out_bytes(p->subs[(uint32_t)p->sub_of[i]].batch, (uint32_t)p->slot[i]);
+        }
+    p->t.headers_ms = c.t1 - c.t0, p->t.setup_ms = c.t2 - c.t1, p->t.entropy_and_upload_ms = c.t3 - c.t2;
+    p->t.kernels_ms = 0.0;  // overlapped: see drain_ms
+    p->t.download_ms = t4 - c.t3, p->t.total_ms = t4 - c.t0, p->t.decode_ms = t4 - c.t0;
+    p->t.images_ok = okc, p->t.pixel_bytes = pixel_bytes, p->t.images_windowed = windowed_images, p->t.images_resized = p->out.w ? okc : 0u;
+    fputs(c.prog_trace.c_str(), stderr);
+    p->t.cpu_ms = process_cpu_ms() - c.cpu0;
+}
+
+extern "C" {
+
+int jpgpu_pipeline_decode_warped(jpgpu_pipeline *p, const uint8_t *const *data, const size_t *len, const jpgpu_window *windows, const uint8_t *flips,
+                                 const jpgpu_warp *warps, uint32_t n, uint32_t flags) {
+    jpgpu::TraceRange roctx_range("jpgpu_pipeline_decode");
+    // (unknown bits are refused, not ignored: 8u was round 2-3's JPGPU_PIPELINE_PROGRESSIVE_DELTAS, removed in round 4 — a caller built
+    // against that header would otherwise silently get another transport: ADVICE r4)
+    constexpr uint32_t kKnownFlags = JPGPU_PIPELINE_DOWNLOAD | JPGPU_PIPELINE_DENSE | JPGPU_PIPELINE_DEVICE_ENTROPY | JPGPU_PIPELINE_GATHER |
+                                     JPGPU_PIPELINE_HOST_LIGHT | JPGPU_PIPELINE_HOST_STAGED | JPGPU_PIPELINE_INPUT_PINNED | JPGPU_PIPELINE_PROGRESSIVE_ON_HOST;
+    if (p && (flags & ~kKnownFlags)) return jpgpu::set_err(p->err, JPGPU_ERR_FORMAT, "jpgpu_pipeline_decode: unknown flag bits 0x%x (this library: %s)", flags & ~kKnownFlags, jpgpu_version());
+    // (the output options among themselves — a tensor output, RGB output, a filter, a warp need an output size —, a fit likewise, flips a
+    // tensor output, warps warp options: refused before anything is decoded)
+    std::string why;
+    if (p && jpgpu::output_rule(p->out, why) != JPGPU_OK) return jpgpu::set_err(p->err, JPGPU_ERR_FORMAT, "jpgpu_pipeline_decode: %s (jpgpu_pipeline_set_output_size)", why.c_str());
+    if (p && p->fit_on() && !p->out.w) return jpgpu::set_err(p->err, JPGPU_ERR_FORMAT, "jpgpu_pipeline_decode: a fit needs an output size (jpgpu_pipeline_set_output_size)");
+    if (p && flips && !p->out.tensor) return jpgpu::set_err(p->err, JPGPU_ERR_FORMAT, "jpgpu_pipeline_decode_augmented: flips need a tensor output (jpgpu_pipeline_set_tensor_output)");
+    if (p && warps && !p->out.warp) return jpgpu::set_err(p->err, JPGPU_ERR_FORMAT, "jpgpu_pipeline_decode_warped: warps need warp options (jpgpu_pipeline_set_warp)");
+    if (p && !p->children.empty()) return (n && (!data || !len)) ? JPGPU_ERR_FORMAT : multi_decode(p, data, len, windows, flips, warps, n, flags);
+    if (!p || !p->pool || (n && (!data || !len))) return JPGPU_ERR_FORMAT;
+    if ((flags & JPGPU_PIPELINE_GATHER) && !p->gather_on) flags &= ~(uint32_t)JPGPU_PIPELINE_GATHER;  // (one device: the pixels are where a gather would put them)
+    int rc = jpgpu::use_device(p->device, p->err);
+    if (rc) return rc;
+    Call c{p, data, len, windows, flips, warps, n, flags};
+    c.t0 = now_ms(), c.cpu0 = process_cpu_ms();
+    c.download = (flags & JPGPU_PIPELINE_DOWNLOAD) != 0, c.compact = (flags & JPGPU_PIPELINE_DENSE) == 0, c.device_entropy = (flags & JPGPU_PIPELINE_DEVICE_ENTROPY) != 0;
+    c.device_progressive = c.device_entropy && (flags & JPGPU_PIPELINE_PROGRESSIVE_ON_HOST) == 0 && !getenv("JPGPU_PIPE_PROGRESSIVE_ON_HOST");
+    p->n = n;
+    p->fes.clear();
+    p->fes.resize(n);
+    p->has_frame.assign(n, 0);
+    p->status.assign(n, JPGPU_ERR_INTERNAL);
+    p->errors.assign(n, std::string());
+    p->infos.assign(n, jpgpu_image_info{});
+    p->wins.assign(n, jpgpu_window{0, 0, 0, 0});
+    p->places.assign(n, jpgpu_placement{0, 0, 0, 0});
+    p->sub_of.assign(n, -1);
+    p->plans.assign(n, {});
+    p->prog_plans.assign(n, {});
+    p->slot.assign(n, -1);
+    p->n_subs = 0;
+    p->downloaded = c.download;
+    p->path.clear();
+    p->t = jpgpu_pipeline_timings{};
+    p->t.threads = p->pool->size() + p->stage_pool->size();  // (+ one uploader thread per call, which mostly waits)
+    c.cand.resize(n);
+    c.win.assign(windows ? n : 0u, jpgpu_window{0, 0, 0, 0});
+
+    // 1. headers
+    p->pool->run(n, [&](uint32_t i) { read_header(c, i); });
+    for (uint32_t i = 0; i < n && windows && !c.any_window; i++) c.any_window = p->status[i] == JPGPU_OK && c.win[i].w != 0;
+    if (c.device_entropy) keep_on_host_what_the_device_would_decode_slower(p, data, len, n);
+    c.n_prog_dev = c.device_progressive ? progressive_share_for_the_device(p, data, len, n) : 0u;
+    c.t1 = now_ms();
+
+    // 2. sub-batches of the images that have a frame (each kept while its geometry sequence repeats)
+    rc = deal_images(c);
+    if (rc) return rc;
+    if (c.ok.empty()) {
+        p->t.headers_ms = c.t1 - c.t0;
+        p->t.total_ms = now_ms() - c.t0;
+        return JPGPU_OK;
+    }
+    p->n_subs = (uint32_t)c.bounds.size() - 1u;
+    for (uint32_t j = 0; j < p->n_subs && rc == JPGPU_OK; j++) rc = prepare_sub_batch(c, j);
+    p->gather_bytes = 0;
+    if (rc == JPGPU_OK && p->gather_on) rc = setup_gather(p, p->n_subs);
+    if (rc) return rc;
+    c.t2 = now_ms();
+
+    // 3. entropy decoding and uploads, every sub-batch's kernels and download behind its last upload
+    rc = decode_upload_and_launch(c);
+    if (rc) return rc;
+
+    // 4. drain: whatever kernels and downloads are still in flight
+    const bool trace = getenv("JPGPU_PIPE_TRACE") != nullptr;
+    for (uint32_t k = 0; k < kCopyStreams; k++) P_HIP(hipStreamSynchronize(p->copy_streams[k]));
+    for (uint32_t k = 0; k < p->n_compute; k++) P_HIP(hipStreamSynchronize(p->compute[k]));
+    if (trace) fprintf(stderr, "pipeline trace: copy and compute streams drained at +%.2f ms\n", now_ms() - c.t2);
+    if (c.download)
+        for (uint32_t k = 0; k < kD2HStreams; k++) {
+            P_HIP(hipStreamSynchronize(p->d2h[k]));
+            if (trace) fprintf(stderr, "pipeline trace: download stream %u drained at +%.2f ms\n", k, now_ms() - c.t2);
+        }
+    // (a child's gather stream is NOT waited for here: the parent does, after every child has decoded — what it then still waits is the exposed part)
+    finish_timings(c);
+    return JPGPU_OK;
+}
 static const SubBatch *sub_of(const jpgpu_pipeline *p, uint32_t i) {
     if (!p || i >= p->n || p->status[i] != JPGPU_OK || p->sub_of[i] < 0) return nullptr;
     const SubBatch &sb = p->subs[(uint32_t)p->sub_of[i]];
@@ -1522,8 +1490,7 @@ int jpgpu_pipeline_set_output_size(jpgpu_pipeline *p, uint16_t width, uint16_t h
     if ((width != 0 || height != 0) && (width == 0 || height == 0 || width > 2048u || height > 2048u))
         return jpgpu::set_err(p->err, JPGPU_ERR_FORMAT, "output size %ux%u: width and height must be 1..2048 (0 x 0: none)", width, height);
     for (jpgpu_pipeline *c : p->children) jpgpu_pipeline_set_output_size(c, width, height);
-    p->rs_w = width;
-    p->rs_h = height;
+    p->out.w = width, p->out.h = height;
     return JPGPU_OK;
 }
 int jpgpu_pipeline_set_tensor_output(jpgpu_pipeline *p, const jpgpu_tensor_format *format) {
@@ -1531,8 +1498,8 @@ int jpgpu_pipeline_set_tensor_output(jpgpu_pipeline *p, const jpgpu_tensor_forma
     if (format && (jpgpu::tensor_elem_bytes(format->dtype) == 0 || format->reserved != 0))
         return jpgpu::set_err(p->err, JPGPU_ERR_FORMAT, "tensor format: dtype %u, reserved %u (dtype must be 1..3, reserved 0)", format->dtype, format->reserved);
     for (jpgpu_pipeline *c : p->children) jpgpu_pipeline_set_tensor_output(c, format);
-    p->tensor = format != nullptr;
-    p->tn = format ? *format : jpgpu_tensor_format{};
+    p->out.tensor = format != nullptr;
+    p->out.tn = format ? *format : jpgpu_tensor_format{};
     return JPGPU_OK;
 }
 int jpgpu_pipeline_set_fit(jpgpu_pipeline *p, const jpgpu_fit *fit) {
@@ -1541,8 +1508,8 @@ int jpgpu_pipeline_set_fit(jpgpu_pipeline *p, const jpgpu_fit *fit) {
         return jpgpu::set_err(p->err, JPGPU_ERR_FORMAT, "fit: mode %u, size %u, reserved %u (mode must be 0..2, size non-zero for mode 1, reserved 0)", fit->mode, fit->size,
                               fit->reserved);
     for (jpgpu_pipeline *c : p->children) jpgpu_pipeline_set_fit(c, fit);
-    p->fit_on = fit != nullptr && fit->mode != JPGPU_FIT_STRETCH;  // (stretch: every placement is the whole output — no placement at all)
-    p->fit = p->fit_on ? *fit : jpgpu_fit{};
+    p->fit = fit && fit->mode != JPGPU_FIT_STRETCH ? *fit : jpgpu_fit{};  // (stretch: every placement is the whole output — no placement at all)
+    memcpy(p->out.fill, p->fit.fill, 4);
     return JPGPU_OK;
 }
 int jpgpu_pipeline_set_warp(jpgpu_pipeline *p, const jpgpu_warp_options *warp) {
@@ -1550,8 +1517,8 @@ int jpgpu_pipeline_set_warp(jpgpu_pipeline *p, const jpgpu_warp_options *warp) {
     if (warp && (warp->filter > JPGPU_WARP_BILINEAR || warp->reserved != 0))
         return jpgpu::set_err(p->err, JPGPU_ERR_FORMAT, "warp options: filter %u, reserved %u (JPGPU_WARP_NEAREST or JPGPU_WARP_BILINEAR, reserved 0)", warp->filter, warp->reserved);
     for (jpgpu_pipeline *c : p->children) jpgpu_pipeline_set_warp(c, warp);
-    p->warp_on = warp != nullptr;
-    p->warp_opt = warp ? *warp : jpgpu_warp_options{};
+    p->out.warp = warp != nullptr;
+    p->out.wp = warp ? *warp : jpgpu_warp_options{};
     return JPGPU_OK;
 }
 int jpgpu_pipeline_image_placement(const jpgpu_pipeline *p, uint32_t i, jpgpu_placement *out) {
@@ -1564,13 +1531,13 @@ int jpgpu_pipeline_set_filter(jpgpu_pipeline *p, uint32_t filter) {
     if (!p) return JPGPU_ERR_FORMAT;
     if (filter > JPGPU_FILTER_LANCZOS) return jpgpu::set_err(p->err, JPGPU_ERR_FORMAT, "resample filter %u: the ids are 0..4 (JPGPU_FILTER_*)", filter);
     for (jpgpu_pipeline *c : p->children) jpgpu_pipeline_set_filter(c, filter);
-    p->filter = filter;
+    p->out.filter = filter;
     return JPGPU_OK;
 }
 int jpgpu_pipeline_set_rgb_output(jpgpu_pipeline *p, int on) {
     if (!p) return JPGPU_ERR_FORMAT;
     for (jpgpu_pipeline *c : p->children) jpgpu_pipeline_set_rgb_output(c, on);
-    p->rgb = on != 0;
+    p->out.rgb = on != 0;
     return JPGPU_OK;
 }
 uint32_t jpgpu_pipeline_device_count(const jpgpu_pipeline *p) { return !p ? 0u : (p->children.empty() ? 1u : (uint32_t)p->children.size()); }

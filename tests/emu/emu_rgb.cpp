@@ -15,7 +15,7 @@ static void hpass_kind(const ResampleJob &j, const int32_t *tab, uint32_t band, 
     else RBand::hpass_of<4u>(j, tab, band, chunk, x0, x1, tid, lds);
 }
 
-// the job of an image of `snc` source channels in a batch with RGB output, as batch_resample_tables makes it
+// the job of an image of `snc` source channels in a batch with RGB output, as output_retable (csrc/batch_output.cpp) makes it
 static bool make_job(ResampleJob &j, std::vector<int32_t> &tab, const uint8_t *src, uint32_t in_w, uint32_t in_h, uint32_t snc, uint32_t out_w, uint32_t out_h,
                      uint8_t *dst, uint32_t lds_cap, uint32_t rb_cap) {
     j.src = src, j.dst = dst;
