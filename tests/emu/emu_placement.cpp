@@ -1,10 +1,10 @@
 // emu_placement.cpp — TEST-ONLY CPU emulation of the placed kernels (csrc/placed_band.hpp, csrc/placed.hip): the product's range tables,
-// planner and every workgroup of the launch grid, lane by lane and phase by phase (the kernels' barriers are the phase boundaries).
+// planner and every workgroup of the launch grid through the product's own walk (band_walk of csrc/band_walk.hpp under the lanes of
+// band_lanes.hpp: the walk's barriers are the phase boundaries).
 // Built by tests/test_placement_emulation.py (g++, the flags of tests/emu/Makefile) and, with its own main, by the stand-alone
 // sanitizer program tests/emu/placement_asan.cpp.
 #include "hip_shim.hpp"
-#include <vector>
-#include "../../jpeg-decoder_amd/csrc/placed_band.hpp"
+#include "band_lanes.hpp"
 
 using namespace jpgpu;
 
@@ -26,59 +26,12 @@ int plan(ResampleJob &j, Place &p, std::vector<int32_t> &tab, uint32_t in_w, uin
     return placed_plan(j, p, tab.data(), lds_cap, rb_cap) ? 0 : -1;
 }
 
-void hpass_kind(const ResampleJob &j, const int32_t *tab, uint32_t ib, uint32_t chunk, uint32_t x0, uint32_t x1, uint32_t tid, uint8_t *rows) {
-    if (j.src_nc == 1u) RBand::hpass_of<1u>(j, tab, ib, chunk, x0, x1, tid, rows);
-    else if (j.src_nc == 4u) RBand::hpass_of<4u>(j, tab, ib, chunk, x0, x1, tid, rows);
-    else RBand::hpass_of<0u>(j, tab, ib, chunk, x0, x1, tid, rows);
-}
-
 // info: rb, the job's bands, cap_rows, most chunks of a band, lds_bytes, canvas bands, bands above the first visible one, bands without a
 // visible row, bands whose first AND last dword are shared with a neighbour, visible width, visible height, shift
 void fill_info(uint32_t *info, const ResampleJob &j, const Place &p, uint32_t most, uint32_t fill_bands, uint32_t shared) {
     if (!info) return;
     info[0] = j.rb, info[1] = j.bands, info[2] = j.cap_rows, info[3] = most, info[4] = j.lds_bytes, info[5] = p.bands, info[6] = p.pre;
     info[7] = fill_bands, info[8] = shared, info[9] = j.out_w, info[10] = j.out_h, info[11] = p.shift;
-}
-
-template <class E>
-void run_tensor(const PlacedTensorJob &t, const int32_t *tab, const uint32_t *ttab, uint8_t *lds, uint32_t lds_total, uint32_t &most, uint32_t &fill_bands) {
-    typedef int32_t Sum[16];
-    std::vector<int32_t> acc(RS_NT * 16);
-    const ResampleJob &j = t.t.r;
-    for (uint32_t band = 0; band < t.p.bands; band++) {
-        uint32_t R0, R1, ib;
-        bool vis;
-        PBand::band_of(j, t.p, band, R0, R1, ib, vis);
-        memset(lds, 0xCD, lds_total);  // garbage, like real LDS
-        for (uint32_t tid = 0; tid < RS_NT; tid++) TBand<E>::load_table(t.t, ttab, tid, lds);
-        if (!vis) {
-            fill_bands++;
-            memset(lds, 0xCD, j.lds_bytes);  // (a band of fill reads no LDS row)
-            for (uint32_t tid = 0; tid < RS_NT; tid++) PTBand<E>::fill_band(t, band, tid, lds);
-            continue;
-        }
-        uint8_t *rows = lds + t.p.shift;
-        const uint32_t chunks = RBand::chunks_of(j, tab, ib);
-        most = chunks > most ? chunks : most;
-        if (chunks == 1u) {
-            for (uint32_t tid = 0; tid < RS_NT; tid++) hpass_kind(j, tab, ib, 0u, 0u, j.out_w, tid, rows);
-            for (uint32_t tid = 0; tid < RS_NT; tid++) PTBand<E>::vstore(t, tab, band, ib, tid, lds);
-            continue;
-        }
-        const uint32_t groups = PTBand<E>::groups_of(t, band);
-        for (uint32_t group = 0; group < groups; group++) {
-            uint32_t x0, x1;
-            PTBand<E>::group_columns(t, band, group, x0, x1);
-            std::fill(acc.begin(), acc.end(), 0);
-            for (uint32_t chunk = 0; chunk < chunks; chunk++) {
-                memset(lds, 0xCD, j.lds_bytes);  // (the rows only: the table stays)
-                for (uint32_t tid = 0; tid < RS_NT; tid++) hpass_kind(j, tab, ib, chunk, x0, x1, tid, rows);
-                for (uint32_t tid = 0; tid < RS_NT; tid++)
-                    PTBand<E>::vacc(t, tab, band, ib, chunk, group, tid, lds, *reinterpret_cast<Sum *>(&acc[16 * tid]));
-            }
-            for (uint32_t tid = 0; tid < RS_NT; tid++) PTBand<E>::vput(t, band, group, tid, *reinterpret_cast<Sum *>(&acc[16 * tid]), lds);
-        }
-    }
 }
 
 }  // namespace
@@ -95,45 +48,13 @@ int emu_placed(const uint8_t *src, uint32_t in_w, uint32_t in_h, uint32_t nc, ui
     int rc = plan(j, pj.p, tab, in_w, in_h, nc, kind, cw, ch, rw, rh, x, y, fill, lds_cap, rb_cap);
     if (rc) return rc;
     j.src = src, j.dst = dst;
-    std::vector<uint8_t> lds_store(j.lds_bytes + 16);
-    uint8_t *lds = lds_store.data() + ((16 - ((uintptr_t)lds_store.data() & 15)) & 15);
-    typedef int32_t Sum[4];
-    std::vector<int32_t> acc(RS_NT * 4);
     uint32_t most = 0, fill_bands = 0, shared = 0;
     for (uint32_t band = 0; band < pj.p.bands; band++) {
-        uint32_t R0, R1, ib, a, b, q0, q1;
-        bool vis;
-        PBand::band_of(j, pj.p, band, R0, R1, ib, vis);
+        uint32_t a, b, q0, q1;
         PBand::run_of(j, pj.p, band, a, b, q0, q1);
         if ((a & 3u) && (b & 3u) && q1 - q0 >= 2u) shared++;
-        memset(lds, 0xCD, j.lds_bytes);  // garbage, like real LDS
-        if (!vis) {
-            fill_bands++;
-            for (uint32_t tid = 0; tid < RS_NT; tid++) PBand::fill_band(j, pj.p, band, tid);
-            continue;
-        }
-        uint8_t *rows = lds + pj.p.shift;
-        const uint32_t chunks = RBand::chunks_of(j, tab.data(), ib);
-        most = chunks > most ? chunks : most;
-        if (chunks == 1u) {
-            for (uint32_t tid = 0; tid < RS_NT; tid++) hpass_kind(j, tab.data(), ib, 0u, 0u, j.out_w, tid, rows);
-            for (uint32_t tid = 0; tid < RS_NT; tid++) PBand::vstore(j, pj.p, tab.data(), band, ib, tid, lds);
-            continue;
-        }
-        const uint32_t groups = PBand::groups_of(j, pj.p, band);
-        for (uint32_t group = 0; group < groups; group++) {
-            uint32_t x0, x1;
-            PBand::group_columns(j, pj.p, band, group, x0, x1);
-            std::fill(acc.begin(), acc.end(), 0);
-            for (uint32_t chunk = 0; chunk < chunks; chunk++) {
-                memset(lds, 0xCD, j.lds_bytes);
-                for (uint32_t tid = 0; tid < RS_NT; tid++) hpass_kind(j, tab.data(), ib, chunk, x0, x1, tid, rows);
-                for (uint32_t tid = 0; tid < RS_NT; tid++)
-                    PBand::vacc(j, pj.p, tab.data(), band, ib, chunk, group, tid, lds, *reinterpret_cast<Sum *>(&acc[4 * tid]));
-            }
-            for (uint32_t tid = 0; tid < RS_NT; tid++) PBand::vput(j, pj.p, band, group, tid, *reinterpret_cast<Sum *>(&acc[4 * tid]));
-        }
     }
+    emu_launch_placed(pj, tab.data(), most, fill_bands);
     fill_info(info, j, pj.p, most, fill_bands, shared);
     return 0;
 }
@@ -155,12 +76,9 @@ int emu_placed_tensor(const uint8_t *src, uint32_t in_w, uint32_t in_h, uint32_t
     t.t.flip = flip;
     std::vector<uint32_t> ttab(4 * 256, 0xDEADBEEFu);
     tensor_table(dtype, mean, std_, onc, ttab.data());
-    const uint32_t lds_total = ((j.lds_bytes + 15u) & ~15u) + TN_TABLE_MAX;
-    std::vector<uint8_t> lds_store(lds_total + 16);
-    uint8_t *lds = lds_store.data() + ((16 - ((uintptr_t)lds_store.data() & 15)) & 15);
     uint32_t most = 0, fill_bands = 0;
-    if (tensor_elem_bytes(dtype) == 4u) run_tensor<uint32_t>(t, tab.data(), ttab.data(), lds, lds_total, most, fill_bands);
-    else run_tensor<uint16_t>(t, tab.data(), ttab.data(), lds, lds_total, most, fill_bands);
+    if (tensor_elem_bytes(dtype) == 4u) emu_launch_placed_tensor<uint32_t>(t, tab.data(), ttab.data(), most, fill_bands);
+    else emu_launch_placed_tensor<uint16_t>(t, tab.data(), ttab.data(), most, fill_bands);
     fill_info(info, j, t.p, most, fill_bands, 0);
     return 0;
 }

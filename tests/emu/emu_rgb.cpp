@@ -1,19 +1,12 @@
 // emu_rgb.cpp — TEST-ONLY CPU emulation of the RGB-output kernels (resample_band_rgb_kernel / resample_tensor_rgb_kernel of
-// csrc/resample.hip): the product's tables, planner and every workgroup of the launch grid, lane by lane and phase by
-// phase (the kernels' barriers are the phase boundaries), the horizontal pass chosen by the job's src_nc as the kernels choose it.
+// csrc/resample.hip): the product's tables, planner and every workgroup of the launch grid through the product's own walk
+// (band_walk of csrc/band_walk.hpp under the lanes of band_lanes.hpp: the walk's barriers are the phase boundaries), the horizontal
+// pass chosen by the job's src_nc as the kernels choose it.
 // Built by tests/test_rgb_emulation.py (g++, the flags of tests/emu/Makefile).
 #include "hip_shim.hpp"
-#include <vector>
-#include "../../jpeg-decoder_amd/csrc/tensor_band.hpp"
+#include "band_lanes.hpp"
 
 using namespace jpgpu;
-
-// the kernels' dispatch: src_nc 0 -> the three-channel pass, 1 -> gray, anything else -> CMYK
-static void hpass_kind(const ResampleJob &j, const int32_t *tab, uint32_t band, uint32_t chunk, uint32_t x0, uint32_t x1, uint32_t tid, uint8_t *lds) {
-    if (j.src_nc == 0u) RBand::hpass_of<0u>(j, tab, band, chunk, x0, x1, tid, lds);
-    else if (j.src_nc == 1u) RBand::hpass_of<1u>(j, tab, band, chunk, x0, x1, tid, lds);
-    else RBand::hpass_of<4u>(j, tab, band, chunk, x0, x1, tid, lds);
-}
 
 // the job of an image of `snc` source channels in a batch with RGB output, as output_retable (csrc/batch_output.cpp) makes it
 static bool make_job(ResampleJob &j, std::vector<int32_t> &tab, const uint8_t *src, uint32_t in_w, uint32_t in_h, uint32_t snc, uint32_t out_w, uint32_t out_h,
@@ -29,35 +22,6 @@ static bool make_job(ResampleJob &j, std::vector<int32_t> &tab, const uint8_t *s
     return resample_plan(j, tab.data(), lds_cap, rb_cap);
 }
 
-template <class E>
-static void run_tensor_bands(const TensorJob &t, const int32_t *tab, const uint32_t *ttab, uint8_t *lds, uint32_t lds_total, uint32_t &most) {
-    typedef int32_t Sum[16];
-    std::vector<int32_t> acc(RS_NT * 16);
-    for (uint32_t band = 0; band < t.r.bands; band++) {
-        const uint32_t chunks = RBand::chunks_of(t.r, tab, band);
-        most = chunks > most ? chunks : most;
-        memset(lds, 0xCD, lds_total);  // garbage, like real LDS
-        for (uint32_t tid = 0; tid < RS_NT; tid++) TBand<E>::load_table(t, ttab, tid, lds);
-        if (chunks == 1u) {
-            for (uint32_t tid = 0; tid < RS_NT; tid++) hpass_kind(t.r, tab, band, 0u, 0u, t.r.out_w, tid, lds);
-            for (uint32_t tid = 0; tid < RS_NT; tid++) TBand<E>::vstore(t, tab, band, tid, lds);
-            continue;
-        }
-        const uint32_t groups = TBand<E>::groups_of(t, band);
-        for (uint32_t group = 0; group < groups; group++) {
-            uint32_t x0, x1;
-            TBand<E>::group_columns(t, band, group, x0, x1);
-            std::fill(acc.begin(), acc.end(), 0);
-            for (uint32_t chunk = 0; chunk < chunks; chunk++) {
-                memset(lds, 0xCD, t.r.lds_bytes);  // (the rows only: the table stays)
-                for (uint32_t tid = 0; tid < RS_NT; tid++) hpass_kind(t.r, tab, band, chunk, x0, x1, tid, lds);
-                for (uint32_t tid = 0; tid < RS_NT; tid++) TBand<E>::vacc(t, tab, band, chunk, group, tid, lds, *reinterpret_cast<Sum *>(&acc[16 * tid]));
-            }
-            for (uint32_t tid = 0; tid < RS_NT; tid++) TBand<E>::vput(t, band, group, tid, *reinterpret_cast<Sum *>(&acc[16 * tid]), lds);
-        }
-    }
-}
-
 extern "C" {
 // `src`: in_h rows of in_w * snc bytes (snc = 1: any alignment; 4: 4-byte aligned; 3: any); `dst` (4-byte aligned): out_h * out_w * 3
 // bytes.  lds_cap / rb_cap: the planner's budget.  info = {rb, bands, cap_rows, most chunks of a band, lds_bytes, pitch}.  Returns 0,
@@ -68,32 +32,8 @@ int emu_rgb_resample(const uint8_t *src, uint32_t in_w, uint32_t in_h, uint32_t 
     std::vector<int32_t> tabv;
     if (!make_job(j, tabv, src, in_w, in_h, snc, out_w, out_h, dst, lds_cap, rb_cap)) return -1;
     const int32_t *tab = tabv.data();
-    std::vector<uint8_t> lds_store(j.lds_bytes + 16);
-    uint8_t *lds = lds_store.data() + ((16 - ((uintptr_t)lds_store.data() & 15)) & 15);
-    std::vector<int32_t> acc(RS_NT * 4);
     uint32_t most = 0;
-    for (uint32_t band = 0; band < j.bands; band++) {
-        const uint32_t chunks = RBand::chunks_of(j, tab, band);
-        most = chunks > most ? chunks : most;
-        memset(lds, 0xCD, j.lds_bytes);  // garbage, like real LDS
-        if (chunks == 1u) {
-            for (uint32_t t = 0; t < RS_NT; t++) hpass_kind(j, tab, band, 0u, 0u, j.out_w, t, lds);
-            for (uint32_t t = 0; t < RS_NT; t++) RBand::vstore(j, tab, band, t, lds);
-            continue;
-        }
-        const uint32_t groups = RBand::groups_of(j, band);
-        for (uint32_t group = 0; group < groups; group++) {
-            uint32_t x0, x1;
-            RBand::group_columns(j, band, group, x0, x1);
-            std::fill(acc.begin(), acc.end(), 0);
-            for (uint32_t chunk = 0; chunk < chunks; chunk++) {
-                memset(lds, 0xCD, j.lds_bytes);
-                for (uint32_t t = 0; t < RS_NT; t++) hpass_kind(j, tab, band, chunk, x0, x1, t, lds);
-                for (uint32_t t = 0; t < RS_NT; t++) RBand::vacc(j, tab, band, chunk, group, t, lds, *reinterpret_cast<int32_t(*)[4]>(&acc[4 * t]));
-            }
-            for (uint32_t t = 0; t < RS_NT; t++) RBand::vput(j, band, group, t, *reinterpret_cast<int32_t(*)[4]>(&acc[4 * t]));
-        }
-    }
+    emu_launch_u8(j, tab, most);
     if (info) info[0] = j.rb, info[1] = j.bands, info[2] = j.cap_rows, info[3] = most, info[4] = j.lds_bytes, info[5] = j.pitch;
     return 0;
 }
@@ -110,12 +50,9 @@ int emu_rgb_tensor(const uint8_t *src, uint32_t in_w, uint32_t in_h, uint32_t sn
     t.flip = flip;
     std::vector<uint32_t> ttab(4 * 256, 0xDEADBEEFu);
     tensor_table(dtype, mean, std_, 3u, ttab.data());
-    const uint32_t lds_total = ((t.r.lds_bytes + 15u) & ~15u) + TN_TABLE_MAX;
-    std::vector<uint8_t> lds_store(lds_total + 16);
-    uint8_t *lds = lds_store.data() + ((16 - ((uintptr_t)lds_store.data() & 15)) & 15);
     uint32_t most = 0;
-    if (tensor_elem_bytes(dtype) == 4u) run_tensor_bands<uint32_t>(t, tabv.data(), ttab.data(), lds, lds_total, most);
-    else run_tensor_bands<uint16_t>(t, tabv.data(), ttab.data(), lds, lds_total, most);
+    if (tensor_elem_bytes(dtype) == 4u) emu_launch_tensor<uint32_t>(t, tabv.data(), ttab.data(), most);
+    else emu_launch_tensor<uint16_t>(t, tabv.data(), ttab.data(), most);
     if (info) info[0] = t.r.rb, info[1] = t.r.bands, info[2] = t.r.cap_rows, info[3] = most, info[4] = t.r.lds_bytes, info[5] = t.r.pitch;
     return 0;
 }

@@ -1,40 +1,11 @@
 // emu_tensor.cpp — TEST-ONLY CPU emulation of the tensor kernel (csrc/tensor_band.hpp, resample_tensor_kernel of csrc/resample.hip): the
-// product's tables, planner and every workgroup of the launch grid, lane by lane and phase by phase (the kernel's barriers are the
-// phase boundaries).  Built by tests/test_tensor_emulation.py (g++, the flags of tests/emu/Makefile).
+// product's tables, planner and every workgroup of the launch grid through the product's own walk (band_walk of csrc/band_walk.hpp
+// under the lanes of band_lanes.hpp: the walk's barriers are the phase boundaries).  Built by tests/test_tensor_emulation.py (g++, the
+// flags of tests/emu/Makefile).
 #include "hip_shim.hpp"
-#include <vector>
-#include "../../jpeg-decoder_amd/csrc/tensor_band.hpp"
+#include "band_lanes.hpp"
 
 using namespace jpgpu;
-
-template <class E>
-static void run_bands(const TensorJob &t, const int32_t *tab, const uint32_t *ttab, uint8_t *lds, uint32_t lds_total, uint32_t &most) {
-    typedef int32_t Sum[16];
-    std::vector<int32_t> acc(RS_NT * 16);
-    for (uint32_t band = 0; band < t.r.bands; band++) {
-        const uint32_t chunks = RBand::chunks_of(t.r, tab, band);
-        most = chunks > most ? chunks : most;
-        memset(lds, 0xCD, lds_total);  // garbage, like real LDS
-        for (uint32_t tid = 0; tid < RS_NT; tid++) TBand<E>::load_table(t, ttab, tid, lds);
-        if (chunks == 1u) {
-            for (uint32_t tid = 0; tid < RS_NT; tid++) RBand::hpass(t.r, tab, band, 0u, 0u, t.r.out_w, tid, lds);
-            for (uint32_t tid = 0; tid < RS_NT; tid++) TBand<E>::vstore(t, tab, band, tid, lds);
-            continue;
-        }
-        const uint32_t groups = TBand<E>::groups_of(t, band);
-        for (uint32_t group = 0; group < groups; group++) {
-            uint32_t x0, x1;
-            TBand<E>::group_columns(t, band, group, x0, x1);
-            std::fill(acc.begin(), acc.end(), 0);
-            for (uint32_t chunk = 0; chunk < chunks; chunk++) {
-                memset(lds, 0xCD, t.r.lds_bytes);  // (the rows only: the table stays)
-                for (uint32_t tid = 0; tid < RS_NT; tid++) RBand::hpass(t.r, tab, band, chunk, x0, x1, tid, lds);
-                for (uint32_t tid = 0; tid < RS_NT; tid++) TBand<E>::vacc(t, tab, band, chunk, group, tid, lds, *reinterpret_cast<Sum *>(&acc[16 * tid]));
-            }
-            for (uint32_t tid = 0; tid < RS_NT; tid++) TBand<E>::vput(t, band, group, tid, *reinterpret_cast<Sum *>(&acc[16 * tid]), lds);
-        }
-    }
-}
 
 extern "C" {
 // `src` (any alignment): in_h rows of in_w * nc bytes; `dst` (16-byte aligned): nc planes of `plane` elements (0: out_h * out_w), the
@@ -59,12 +30,9 @@ int emu_tensor(const uint8_t *src, uint32_t in_w, uint32_t in_h, uint32_t nc, ui
     t.flip = flip;
     std::vector<uint32_t> ttab(4 * 256, 0xDEADBEEFu);
     tensor_table(dtype, mean, std_, nc, ttab.data());
-    const uint32_t lds_total = ((j.lds_bytes + 15u) & ~15u) + TN_TABLE_MAX;
-    std::vector<uint8_t> lds_store(lds_total + 16);
-    uint8_t *lds = lds_store.data() + ((16 - ((uintptr_t)lds_store.data() & 15)) & 15);
     uint32_t most = 0;
-    if (tensor_elem_bytes(dtype) == 4u) run_bands<uint32_t>(t, tab.data(), ttab.data(), lds, lds_total, most);
-    else run_bands<uint16_t>(t, tab.data(), ttab.data(), lds, lds_total, most);
+    if (tensor_elem_bytes(dtype) == 4u) emu_launch_tensor<uint32_t>(t, tab.data(), ttab.data(), most);
+    else emu_launch_tensor<uint16_t>(t, tab.data(), ttab.data(), most);
     if (info) info[0] = j.rb, info[1] = j.bands, info[2] = j.cap_rows, info[3] = most, info[4] = j.lds_bytes;
     return 0;
 }

@@ -117,6 +117,25 @@ def test_batch_placed_tensor(dtype):
             assert np.array_equal(T.bits(o), want), (i, canvas, pls[i], flips[i], np.argwhere(T.bits(o) != want)[:6].tolist())
 
 
+def test_placed_tensor_chunked_path():
+    """resample_placed_tensor_kernel on the chunked path: a 16 x 1200 image resampled to 16 x 1 and laid at (5, 1) into a 24 x 3 canvas.
+    The one visible row's support is every source row; the LDS rows of 64 bytes (shift 15 + 48, rounded up to 16) hold 512 of them, so
+    the band takes three chunks.  The bands above and below it are fill.  Plain and flipped, float32."""
+    rng = np.random.default_rng(5)
+    case = RZ._case(rng, 16, 1200, [(1, 1)] * 3, "RGB")
+    full = RZ._full(case)
+    canvas, pl, flips = (24, 3), (16, 1, 5, 1), [False, True]
+    vb, _ = J.resample_coefficients(1200, 1)
+    pitch = (((5 * 3) & 15) + 16 * 3 + 15) & ~15
+    assert int(vb[0].sum()) - int(vb[0, 0]) > min(32 * 1024 // pitch, 1200)  # (the row's source rows against placed_plan's cap_rows)
+    fmt, ref_fmt = TN.fmt_of("float32")
+    outs, path = _decode([case, case], None, canvas, [pl, pl], fmt, flips, fill=(114, 7, 200))
+    assert path.endswith("+place+resize+tensor"), path
+    u8 = want_u8(case, full, None, canvas, pl, (114, 7, 200, 0))
+    for o, flip in zip(outs, flips):
+        assert np.array_equal(T.bits(o), T.bits(T.to_tensor(u8, T.table(ref_fmt, 3), flip))), flip
+
+
 def test_rgb_output_with_pad_placements():
     """A gray and a CMYK file padded on both axes: the fill is in RGB order."""
     rng = np.random.default_rng(9)
