@@ -377,6 +377,45 @@ int jpgpu_batch_set_warps(jpgpu_batch *b, const jpgpu_warp *warps);
  * int holds gives INT32_MAX, one that is no number -1. */
 int jpgpu_warp_check(const jpgpu_warp *warp, uint32_t out_w, uint32_t out_h);
 int jpgpu_warp_nearest_axis(double a, double b, uint32_t out_size, int32_t *idx);
+/* ---- EXIF orientation in front of the fixed output size ------------------------------------------------------------
+ * jpgpu_batch_create_warped with an orientation per image (`orientations`: n_images bytes, each 1..8).  Let S be what image i gives the
+ * resample without it: its whole output in the grid after the DCT scale, H x W x nc interleaved.  The oriented image O is Pillow's
+ * Image.transpose(method) under ImageOps.exif_transpose's mapping:
+ *     o  Pillow            O's size   O[y][x]
+ *     1  none              W x H      S[y][x]
+ *     2  FLIP_LEFT_RIGHT   W x H      S[y][W-1-x]
+ *     3  ROTATE_180        W x H      S[H-1-y][W-1-x]
+ *     4  FLIP_TOP_BOTTOM   W x H      S[H-1-y][x]
+ *     5  TRANSPOSE         H x W      S[x][y]
+ *     6  ROTATE_270        H x W      S[H-1-x][y]
+ *     7  TRANSVERSE        H x W      S[H-1-x][W-1-y]
+ *     8  ROTATE_90         H x W      S[x][W-1-y]
+ * With an orientation, everything the output stage defines on "the image" is defined on O: the window is (x, y, w, h) inside O, checked
+ * against O's size; the fit rules and jpgpu_fit_placement take the oriented window's size; the RGB conversion, the resample (the
+ * horizontal pass first, on O's rows), placement, flip, warp and tensor table follow unchanged.  In Pillow's terms:
+ * ImageOps.exif_transpose(Image.open(f)), then .convert("RGB"), then the crop, the resize and so on, as documented above.
+ * On the host the oriented window is mapped back to the window of S whose orientation it is (jpgpu_oriented_window); the batch's pixel
+ * routes decode that source window as ever — the window rule applies to it — and one launch behind them, in front of the resample
+ * launch on the same stream, rewrites the source window of every image with o != 1, oriented and packed, into a second arena the batch
+ * owns, where that image's resample reads.  Images with o == 1 are not touched.  jpgpu_batch_path gains "+orient" in front of "+rgb" /
+ * "+place" / "+resize".  `orientations` NULL, or all ones, IS jpgpu_batch_create_warped: the same kernels, launches, bytes and path.
+ * Refusals: a value outside 1..8: JPGPU_ERR_FORMAT; orientations other than 1 without an output size: JPGPU_ERR_UNSUPPORTED with the
+ * reason in jpgpu_batch_last_error, as RGB output; planar ColorTransform None images stay JPGPU_ERR_UNSUPPORTED.
+ * Differences from Pillow: the orientation is what the caller passes — jpgpu_exif_orientation reads the EXIF tag alone, where
+ * ImageOps.exif_transpose falls back to the XMP packet's tiff:Orientation when the file has no EXIF tag: XMP is ignored here. */
+int jpgpu_batch_create_oriented(int device, const jpgpu_image_desc *descs, const jpgpu_window *windows, const jpgpu_placement *placements,
+                                const uint8_t *fill, uint16_t out_w, uint16_t out_h, const jpgpu_tensor_format *format,
+                                const jpgpu_warp_options *warp, const uint8_t *orientations, uint32_t n_images, uint32_t flags, jpgpu_batch **out);
+/* Pure host functions (no device needed).  jpgpu_oriented_window: for a source of w x h (1..65535 each) under `orientation`, O's size
+ * into *oriented_w / *oriented_h and the window `oriented` of O (NULL, or w == 0 or h == 0: all of it, which stays "all") as the window
+ * of S into *source; any output may be NULL.  An orientation outside 1..8, a size of 0 or a window outside O: JPGPU_ERR_FORMAT.
+ * jpgpu_exif_orientation: the orientation an EXIF blob states — `exif` is the payload behind "Exif\0\0" (jpgpu_decoder_exif_data): the
+ * TIFF header ("II" or "MM", magic 42), IFD0's offset, its 12-byte entries, tag 0x0112 of type SHORT and count 1 with a value of 1..8.
+ * Anything else — no EXIF (NULL or len 0), a truncated or out-of-bounds IFD, another type or count, a value outside 1..8 — gives 1,
+ * never an error; every read is checked against len. */
+int jpgpu_oriented_window(uint32_t orientation, uint32_t w, uint32_t h, const jpgpu_window *oriented, uint32_t *oriented_w, uint32_t *oriented_h,
+                          jpgpu_window *source);
+uint32_t jpgpu_exif_orientation(const uint8_t *exif, size_t len);
 void jpgpu_batch_destroy(jpgpu_batch *b);
 const char *jpgpu_batch_last_error(const jpgpu_batch *b);
 

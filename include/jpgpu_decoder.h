@@ -248,6 +248,17 @@ int jpgpu_pipeline_set_tensor_output(jpgpu_pipeline *p, const jpgpu_tensor_forma
  * hold / count the three-channel bytes; jpgpu_pipeline_image_info keeps reporting the file's own components and pixel format.
  * Switching it on or off between calls creates the kept sub-batches anew, as a changed output size does. */
 int jpgpu_pipeline_set_rgb_output(jpgpu_pipeline *p, int on);
+/* EXIF orientation for every image of the calls that follow (sticky, like RGB output; 0: off, the default — same routes, kernels,
+ * launches and bytes as ever).  The header step reads every file's orientation (jpgpu_exif_orientation of its EXIF segment: 1 for a
+ * file without the tag or with a damaged one, never an error; XMP is not read) and the sub-batches are created with
+ * jpgpu_batch_create_oriented (jpgpu.h): the image is oriented in front of the output size, as ImageOps.exif_transpose does, and the
+ * call's windows and the fit are meant on, and checked against, the ORIENTED image.  It needs an output size: with none in force the
+ * next decode fails as a whole with JPGPU_ERR_FORMAT before anything is decoded.  jpgpu_pipeline_image_orientation returns the
+ * orientation applied to image i of the last call (1 when the option is off); jpgpu_pipeline_image_info keeps the file's own size;
+ * jpgpu_pipeline_image_window the window as given, in oriented coordinates (none given: the whole oriented grid).  A kept sub-batch is
+ * reused only for the same orientations, image by image; other orientations create it anew, as a changed output size does. */
+int jpgpu_pipeline_set_exif_orientation(jpgpu_pipeline *p, int on);
+int jpgpu_pipeline_image_orientation(const jpgpu_pipeline *p, uint32_t i);
 /* The resample filter for every image of the calls that follow (sticky, like the output size): one of JPGPU_FILTER_* (jpgpu.h); the
  * sub-batches are created with JPGPU_BATCH_FILTER(filter).  JPGPU_FILTER_BILINEAR (0) is the default: the tables, kernels, bytes and path
  * string of the output size alone.  Another filter needs an output size: with none in force the next decode fails as a whole with

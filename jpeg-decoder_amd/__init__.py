@@ -5,8 +5,8 @@ compute_image_parallel), the batch driver and the Decoder front-end.  The produc
 HIP-only: nothing here falls back to a CPU implementation."""
 from . import _native
 from ._native import Component, ImageDesc, build, device_count, lib, process_init
-from .batch import (Batch, Fit, TensorFormat, WarpOptions, fit_placement, image_desc, resample_coefficients, rotate_matrix, warp_check,
-                    warp_nearest_axis)
+from .batch import (Batch, Fit, TensorFormat, WarpOptions, exif_orientation, fit_placement, image_desc, oriented_size, oriented_window,
+                    resample_coefficients, rotate_matrix, warp_check, warp_nearest_axis)
 from .decoder import CODING_PROCESSES, PIXEL_FORMATS, Decoder, ImageInfo, decode_batch
 from .error import Error, FormatError, InternalError, IoError, NoDeviceError, UnsupportedError
 from .pipeline import PinnedFiles, Pipeline
@@ -14,7 +14,7 @@ from .parser import Dimensions, choose_idct_size, make_components, scaled_output
 from .worker import COLOR_TRANSFORMS, HipWorker, RowData, color_transform_id, compute_image_parallel
 
 __all__ = [
-    "Batch", "Fit", "WarpOptions", "rotate_matrix", "warp_check", "warp_nearest_axis", "fit_placement", "resample_coefficients", "CODING_PROCESSES", "COLOR_TRANSFORMS", "Component", "Decoder", "Dimensions", "ImageInfo", "PIXEL_FORMATS", "PinnedFiles", "Pipeline", "TensorFormat", "decode_batch", "Error", "FormatError", "HipWorker", "ImageDesc",
+    "Batch", "Fit", "WarpOptions", "exif_orientation", "oriented_size", "oriented_window", "rotate_matrix", "warp_check", "warp_nearest_axis", "fit_placement", "resample_coefficients", "CODING_PROCESSES", "COLOR_TRANSFORMS", "Component", "Decoder", "Dimensions", "ImageInfo", "PIXEL_FORMATS", "PinnedFiles", "Pipeline", "TensorFormat", "decode_batch", "Error", "FormatError", "HipWorker", "ImageDesc",
     "InternalError", "IoError", "NoDeviceError", "RowData", "UnsupportedError", "build", "choose_idct_size",
     "color_transform_id", "compute_image_parallel", "device_count", "image_desc", "lib", "make_components",
     "scaled_output_size", "update_component_sizes",

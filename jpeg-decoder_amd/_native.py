@@ -174,6 +174,10 @@ _PROTOS = {
     "jpgpu_batch_create_warped": (C.c_int, [C.c_int, C.POINTER(ImageDesc), C.POINTER(Window), C.POINTER(Placement), C.c_void_p, C.c_uint16, C.c_uint16,
                                             C.POINTER(TensorFormatStruct), C.POINTER(WarpOptionsStruct), C.c_uint32, C.c_uint32, C.POINTER(C.c_void_p)]),
     "jpgpu_batch_set_warps": (C.c_int, [C.c_void_p, C.POINTER(Warp)]),
+    "jpgpu_batch_create_oriented": (C.c_int, [C.c_int, C.POINTER(ImageDesc), C.POINTER(Window), C.POINTER(Placement), C.c_void_p, C.c_uint16, C.c_uint16,
+                                              C.POINTER(TensorFormatStruct), C.POINTER(WarpOptionsStruct), C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(C.c_void_p)]),
+    "jpgpu_oriented_window": (C.c_int, [C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(Window), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(Window)]),
+    "jpgpu_exif_orientation": (C.c_uint32, [C.c_void_p, C.c_size_t]),
     "jpgpu_warp_check": (C.c_int, [C.POINTER(Warp), C.c_uint32, C.c_uint32]),
     "jpgpu_warp_nearest_axis": (C.c_int, [C.c_double, C.c_double, C.c_uint32, C.c_void_p]),
     "jpgpu_tensor_table": (C.c_int, [C.POINTER(TensorFormatStruct), C.c_uint32, C.c_void_p]),
@@ -254,6 +258,8 @@ _PROTOS = {
     "jpgpu_pipeline_set_tensor_output": (C.c_int, [C.c_void_p, C.POINTER(TensorFormatStruct)]),
     "jpgpu_pipeline_set_rgb_output": (C.c_int, [C.c_void_p, C.c_int]),
     "jpgpu_pipeline_set_filter": (C.c_int, [C.c_void_p, C.c_uint32]),
+    "jpgpu_pipeline_set_exif_orientation": (C.c_int, [C.c_void_p, C.c_int]),
+    "jpgpu_pipeline_image_orientation": (C.c_int, [C.c_void_p, C.c_uint32]),
     "jpgpu_pipeline_set_fit": (C.c_int, [C.c_void_p, C.POINTER(FitStruct)]),
     "jpgpu_pipeline_image_placement": (C.c_int, [C.c_void_p, C.c_uint32, C.POINTER(Placement)]),
     "jpgpu_pipeline_set_color_transform": (C.c_int, [C.c_void_p, C.c_int]),

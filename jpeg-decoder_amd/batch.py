@@ -264,6 +264,44 @@ def flip_bytes(flips, n):
     return (C.c_uint8 * max(n, 1))(*flips)
 
 
+def orientation_bytes(orientations, n):
+    """`orientations`: None or one EXIF orientation (1..8; None: 1) per image -> (ctypes array of n bytes or None).  A value outside
+    0..255 is a ValueError; one outside 1..8 is for the library to refuse (FormatError)."""
+    if orientations is None:
+        return None
+    vals = [1 if o is None else int(o) for o in orientations]
+    if len(vals) != n:
+        raise ValueError(f"{len(vals)} orientations for {n} images")
+    if any(v < 0 or v > 255 for v in vals):
+        raise ValueError(f"orientations {vals!r}")
+    return (C.c_uint8 * max(n, 1))(*vals)
+
+
+def exif_orientation(exif):
+    """jpgpu_exif_orientation: the orientation (1..8) an EXIF blob states — the payload behind ``Exif\\0\\0``, as ``Decoder.exif_data()``
+    returns it — and 1 for None, no tag, or anything damaged (pure host function; XMP is not read)."""
+    b = bytes(exif) if exif is not None else b""
+    return int(N.lib().jpgpu_exif_orientation(b, len(b)))
+
+
+def oriented_window(orientation, size, window=None):
+    """jpgpu_oriented_window: for a source of ``size`` = (w, h) under an EXIF orientation -> ((ow, oh), source_window): the oriented
+    image's size, and the window (x, y, w, h) of the oriented image (None: all of it) as the window of the source whose orientation it
+    is (None for all of it).  An orientation outside 1..8 or a window outside the oriented image raises FormatError."""
+    wn = N.Window()
+    if window is not None:
+        wn.x, wn.y, wn.w, wn.h = (int(v) for v in window)
+    ow, oh, src = C.c_uint32(0), C.c_uint32(0), N.Window()
+    check(N.lib().jpgpu_oriented_window(int(orientation), int(size[0]), int(size[1]), C.byref(wn), C.byref(ow), C.byref(oh), C.byref(src)),
+          b"jpgpu_oriented_window: refused")
+    return (ow.value, oh.value), (None if (src.w == 0 or src.h == 0) else (src.x, src.y, src.w, src.h))
+
+
+def oriented_size(orientation, size):
+    """The size (w, h) of the oriented image for a source of ``size`` = (w, h): swapped for the orientations 5..8."""
+    return oriented_window(orientation, size)[0]
+
+
 class Batch:
     """N independent images decoded per launch (jpgpu_batch_*).
 
@@ -306,10 +344,16 @@ class Batch:
     its u8 pixels of the output size, placement fill included, mirrored first when the image is flipped — is then read through six
     coefficients per image, ``Image.transform((w, h), Image.AFFINE, m, NEAREST or BILINEAR, fillcolor=warp.fill)``, and written as bytes
     or, with `tensor`, through the table.  Every image starts with the identity; ``set_warps([...])`` sets the
-    matrices from the next decode on.  `path` gains "+warp" or "+warp:bilinear" before "+tensor"."""
+    matrices from the next decode on.  `path` gains "+warp" or "+warp:bilinear" before "+tensor".
+
+    orientations: None, or one EXIF orientation (1..8) per image (jpgpu_batch_create_oriented; needs an output_size, else
+    UnsupportedError).  Every image is oriented first — ``ImageOps.exif_transpose`` — and everything above is meant on the oriented image:
+    the window lies in it and is checked against its size (``oriented_size``), placements are those of the oriented window, and the
+    resample's horizontal pass runs on its rows.  `path` gains "+orient" in front; all ones is the batch without the
+    argument.  A value outside 1..8 is a FormatError."""
 
     def __init__(self, descs, device=0, flags=N.BATCH_DEFAULT, windows=None, output_size=None, tensor=None, rgb=False, placements=None, fill=None,
-                 filter=None, warp=None):
+                 filter=None, warp=None, orientations=None):
         self._h = C.c_void_p()
         arr = (N.ImageDesc * len(descs))(*descs)
         wins = window_structs(windows, len(descs))
@@ -324,7 +368,15 @@ class Batch:
         pls = placement_structs(placements, len(descs))
         self.fill = fill_tuple(fill)
         self.warp = warp
-        if warp is not None:
+        ors = orientation_bytes(orientations, len(descs))
+        self.orientations = None if ors is None else list(ors)[: len(descs)]
+        if ors is not None and (self.output_size is not None or any(v != 1 for v in self.orientations)):  # (all ones without a size: no argument)
+            w, h = self.output_size if self.output_size is not None else (0, 0)
+            fmt = tensor.struct() if tensor is not None else None
+            wo = warp.struct() if warp is not None else None
+            st = N.lib().jpgpu_batch_create_oriented(device, arr, wins, pls, (C.c_uint8 * 4)(*self.fill), w, h, C.byref(fmt) if fmt is not None else None,
+                                                     C.byref(wo) if wo is not None else None, ors, len(descs), flags, C.byref(self._h))
+        elif warp is not None:
             w, h = self.output_size if self.output_size is not None else (0, 0)
             fmt = tensor.struct() if tensor is not None else None
             wo = warp.struct()

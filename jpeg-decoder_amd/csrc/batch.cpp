@@ -95,9 +95,11 @@ static int batch_refresh_jobs(jpgpu_batch *b, hipStream_t stream = nullptr) {
 
 extern "C" {
 
-// placements: those of jpgpu_batch_create_placed (NULL, or without an output size: none); spec: everything else of the fixed-output stage
+// placements: those of jpgpu_batch_create_placed (NULL, or without an output size: none); orientations: those of
+// jpgpu_batch_create_oriented (NULL: none) — the windows are then windows of the oriented images; spec_: everything else of the
+// fixed-output stage
 static int batch_create(int device, const jpgpu_image_desc *descs, const jpgpu_window *windows, const jpgpu_placement *placements, uint32_t n_images,
-                        uint32_t flags, const OutputSpec &spec, jpgpu_batch **out) {
+                        uint32_t flags, const OutputSpec &spec_, jpgpu_batch **out, const uint8_t *orientations = nullptr) {
     if (!out) return JPGPU_ERR_FORMAT;
     *out = nullptr;
     if (!descs || n_images == 0 || n_images > 65535) return JPGPU_ERR_FORMAT;
@@ -105,7 +107,11 @@ static int batch_create(int device, const jpgpu_image_desc *descs, const jpgpu_w
     *out = b;  // returned even on failure so the caller can read last_error, then destroy
     b->device = device;
     b->flags = flags;
+    OutputSpec spec = spec_;
+    const uint32_t bad = check_orientations(orientations, n_images, spec.orient);  // (all ones is none: the batch without the argument)
+    if (bad < n_images) return set_err(b->err, JPGPU_ERR_FORMAT, "image %u: orientation %u (the values are 1..8)", bad, orientations[bad]);
     b->o.spec = spec;
+    if (spec.orient) b->o.orient.assign(orientations, orientations + n_images);
     const bool resized = spec.sized();
     std::string why;
     int rc = output_rule(spec, why);
@@ -151,7 +157,10 @@ static int batch_create(int device, const jpgpu_image_desc *descs, const jpgpu_w
         if (windows) {
             uint32_t gw = 0, gh = 0;
             WindowGeom wg;
-            rc = window_rule(d, windows[i], windowed, gw, gh, wg, why);
+            jpgpu_window wn = windows[i];
+            if (spec.orient) rc = orient_window_rule(d, orientations[i], wn, why);  // (the source window: what the routes below decode)
+            if (rc) return set_err(b->err, rc, "image %u: %s", i, why.c_str());
+            rc = window_rule(d, wn, windowed, gw, gh, wg, why);
             if (rc) return set_err(b->err, rc, "image %u: %s", i, why.c_str());
             if (windowed) {
                 kind_key[i] = 0;
@@ -217,6 +226,7 @@ static int batch_create(int device, const jpgpu_image_desc *descs, const jpgpu_w
     if (!b->scaled.empty()) b->path = (b->fused.empty() && b->generic_ids.empty()) ? b->scaled_name : "mixed";
     if (!b->win.empty()) b->path = b->path.empty() ? "window" : "mixed";
     if (b->path.empty()) b->path = "generic";
+    if (spec.orient) b->path += "+orient";
     if (spec.rgb) b->path += "+rgb";
     if (b->o.placed) b->path += "+place";
     if (resized) b->path += "+resize";
@@ -299,8 +309,25 @@ int jpgpu_batch_create_placed(int device, const jpgpu_image_desc *descs, const j
 int jpgpu_batch_create_warped(int device, const jpgpu_image_desc *descs, const jpgpu_window *windows, const jpgpu_placement *placements, const uint8_t *fill,
                               uint16_t out_w, uint16_t out_h, const jpgpu_tensor_format *format, const jpgpu_warp_options *warp, uint32_t n_images, uint32_t flags,
                               jpgpu_batch **out) {
-    if (out_w == 0 || out_h == 0) return refuse_no_size(out, warp ? "a warp needs an output size (%ux%u: width and height must be 1..%u)" : kNoSize, out_w, out_h);
-    return batch_create(device, descs, windows, placements, n_images, flags, spec_of(flags, out_w, out_h, format, fill, warp), out);
+    return jpgpu_batch_create_oriented(device, descs, windows, placements, fill, out_w, out_h, format, warp, nullptr, n_images, flags, out);
+}
+int jpgpu_batch_create_oriented(int device, const jpgpu_image_desc *descs, const jpgpu_window *windows, const jpgpu_placement *placements, const uint8_t *fill,
+                                uint16_t out_w, uint16_t out_h, const jpgpu_tensor_format *format, const jpgpu_warp_options *warp, const uint8_t *orientations,
+                                uint32_t n_images, uint32_t flags, jpgpu_batch **out) {
+    if (out_w == 0 || out_h == 0) {
+        bool any = false;
+        const bool valid = check_orientations(orientations, n_images, any) == n_images;
+        if (out && valid && any) {  // (orientations without an output size: the rule's own refusal, as RGB output)
+            std::string why;
+            OutputSpec s;
+            s.orient = true;
+            *out = new jpgpu_batch();
+            return set_err((*out)->err, output_rule(s, why), "%s", why.c_str());
+        }
+        return refuse_no_size(out, !valid ? "an orientation outside 1..8 (output size %ux%u: width and height must be 1..%u)"
+                                   : warp ? "a warp needs an output size (%ux%u: width and height must be 1..%u)" : kNoSize, out_w, out_h);
+    }
+    return batch_create(device, descs, windows, placements, n_images, flags, spec_of(flags, out_w, out_h, format, fill, warp), out, orientations);
 }
 void jpgpu_batch_destroy(jpgpu_batch *b) {
     if (!b) return;
@@ -612,8 +639,8 @@ int jpgpu::copy_device_to_pinned_host(void *host_pinned, const void *d_src, size
 }
 
 int jpgpu::batch_create_with(int device, const jpgpu_image_desc *descs, const jpgpu_window *windows, const jpgpu_placement *placements, uint32_t n_images,
-                             const OutputSpec &spec, jpgpu_batch **out) {
-    return batch_create(device, descs, windows, placements, n_images, JPGPU_BATCH_DEFAULT, spec, out);
+                             const OutputSpec &spec, jpgpu_batch **out, const uint8_t *orientations) {
+    return batch_create(device, descs, windows, placements, n_images, JPGPU_BATCH_DEFAULT, spec, out, orientations);
 }
 // What jpgpu_batch_create_windowed would make of window `wn` on an image of descriptor `d`, without a batch (window_rule,
 // batch_layout.hpp): the pipeline sorts images out one by one before it forms sub-batches (a batch fails creation as a whole).
@@ -641,6 +668,14 @@ int jpgpu::batch_rewindow(jpgpu_batch *b, const jpgpu_window *windows, const jpg
     }
     std::vector<WindowGeom> geoms;
     std::vector<size_t> lens;
+    std::vector<jpgpu_window> source;
+    if (o.route.orient) {  // (windows of the oriented images: the source windows, as at creation)
+        source.assign(windows, windows + b->descs.size());
+        std::string why;
+        for (size_t i = 0; i < source.size(); i++)
+            if (orient_window_rule(b->descs[i], o.orient[i], source[i], why)) return JPGPU_ERR_UNSUPPORTED;
+        windows = source.data();
+    }
     int rc = window_rule_rewindow(b->descs, b->win.ids, b->out_full_len, windows, geoms, lens);
     if (rc) return rc;
     rc = use_device(b->device, b->err);

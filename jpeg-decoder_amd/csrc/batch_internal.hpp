@@ -88,6 +88,7 @@ struct BandGroup {
 // PlacedTensorJobs (n: `jobs[i]` is then the job of image i's visible rectangle, places[i] where it lies).  Tensor records, and a warp's
 // WarpJobs with the N-sep tables behind them ([n WarpJob | n x (w + h) int32]), travel from pinned mirrors on the decode's stream: fresh
 // flips and matrices come with every call of a loader.  A warp reads a second arena (d_wsrc), which the u8 resample then writes.
+// Orientations: a launch in front of the resample and an arena of its own, at the struct's end.
 struct OutputStage {
     OutputSpec spec;
     OutputRoute route;
@@ -111,8 +112,19 @@ struct OutputStage {
     std::vector<uint8_t> flips;    // per image (jpgpu_batch_set_flips)
     std::vector<jpgpu_warp> m;     // per image (jpgpu_batch_set_warps)
     bool tn_dirty = false, wp_dirty = false;  // flips / matrices changed: the records go up before the next decode
+    // Orientations (route.orient; orient_band.hpp): orient[i] per image for the batch's lifetime.  The images with another value than 1
+    // (or_ids, in image order) have a job each in or_jobs, which rewrites the image's pixels in d_pix, oriented, into d_or at
+    // or_off[image] — where the image's resample job then reads.  output_retable lays the arena out, for these images alone.
+    std::vector<uint8_t> orient;
+    std::vector<uint32_t> or_ids;
+    std::vector<size_t> or_off;
+    std::vector<OrientJob> or_jobs;
+    uint8_t *d_or = nullptr;
+    size_t or_cap = 0;
+    OrientJob *d_or_jobs = nullptr;
+    uint32_t or_max_tiles = 0;
     void free() {
-        for (void *d : {(void *)d_pix, (void *)d_wsrc, (void *)d_tab, (void *)d_bpr, d_tn_table, d_jobs, (void *)d_wp_jobs})
+        for (void *d : {(void *)d_pix, (void *)d_wsrc, (void *)d_tab, (void *)d_bpr, d_tn_table, d_jobs, (void *)d_wp_jobs, (void *)d_or, (void *)d_or_jobs})
             if (d) (void)hipFree(d);
         if (h_jobs) (void)hipHostFree(h_jobs);
         if (h_wp_jobs) (void)hipHostFree(h_wp_jobs);

@@ -40,6 +40,38 @@ int output_create(jpgpu_batch *b) {
                           : o.route.resample == Resample::Placed     ? sizeof(PlacedJob) : 2u * sizeof(ResampleJob);
     B_HIP(hipMalloc(&o.d_jobs, (size_t)n * record));
     if (!o.placed) B_HIP(hipMalloc((void **)&o.d_bpr, (size_t)n * sizeof(uint32_t)));
+    if (o.route.orient) {  // (the jobs of the images with another orientation than 1; output_retable lays their arena out)
+        for (uint32_t i = 0; i < n; i++)
+            if (o.orient[i] != 1u) o.or_ids.push_back(i);
+        B_HIP(hipMalloc((void **)&o.d_or_jobs, o.or_ids.size() * sizeof(OrientJob)));
+    }
+    return JPGPU_OK;
+}
+
+// The orientation jobs and their arena from the source sizes in o.jobs (the windows', else the output grids'), and the oriented sizes
+// into o.jobs: the resample of an oriented image reads the oriented window.
+static int orient_retable(jpgpu_batch *b) {
+    OutputStage &o = b->o;
+    o.or_off.assign(b->descs.size(), 0);
+    o.or_jobs.assign(o.or_ids.size(), OrientJob{});
+    o.or_max_tiles = 0;
+    size_t bytes = 0;
+    for (size_t k = 0; k < o.or_ids.size(); k++) {
+        const uint32_t i = o.or_ids[k];
+        ResampleJob &j = o.jobs[i];
+        OrientJob &oj = o.or_jobs[k];
+        oj.w = j.in_w, oj.h = j.in_h, oj.nc = b->descs[i].ncomp, oj.o = o.orient[i];
+        orient_job_tiles(oj);
+        o.or_max_tiles = std::max(o.or_max_tiles, oj.tiles);
+        oriented_size(oj.o, oj.w, oj.h, j.in_w, j.in_h);
+        o.or_off[i] = bytes;
+        bytes += align_up(orient_bytes(oj.w, oj.h, oj.nc), 256);
+    }
+    if (bytes > o.or_cap) {
+        B_HIP(batch_wait_enqueued(b));  // (a decode still queued writes the arena)
+        B_HIP(hipDeviceSynchronize());
+        B_HIP(grow_device(o.d_or, o.or_cap, bytes, b->win.empty() ? bytes : quarter_more(bytes)));
+    }
     return JPGPU_OK;
 }
 
@@ -77,6 +109,14 @@ int output_retable(jpgpu_batch *b) {
         ResampleJob &j = o.jobs[i];
         window_grid(d.components, d.ncomp, d.out_w, d.out_h, j.in_w, j.in_h);
         if (k < b->win.ids.size() && b->win.ids[k] == i) j.in_w = b->win.geoms[k].ww, j.in_h = b->win.geoms[k].wh, k++;
+    }
+    if (o.route.orient) {
+        const int rc = orient_retable(b);
+        if (rc) return rc;
+    }
+    for (uint32_t i = 0; i < n; i++) {
+        const jpgpu_image_desc &d = b->descs[i];
+        ResampleJob &j = o.jobs[i];
         j.nc = d.ncomp, j.out_w = o.spec.w, j.out_h = o.spec.h;
         if (o.spec.rgb) j.nc = 3u, j.src_nc = d.ncomp == 3u ? 0u : d.ncomp;  // (gray / CMYK: converted by the horizontal pass)
         jpgpu_placement pl{(uint16_t)o.spec.w, (uint16_t)o.spec.h, 0, 0};
@@ -194,6 +234,14 @@ int output_bind(jpgpu_batch *b, hipStream_t stream, bool all) {
     }
     if (o.route.resample == Resample::None) return JPGPU_OK;
     for (uint32_t i = 0; i < n; i++) o.jobs[i].src = o.d_pix + o.pix_off[i], o.jobs[i].dst = o.route.warp ? o.d_wsrc + o.wsrc_off[i] : b->d_out + b->out_off[i];
+    if (o.route.orient) {  // (an oriented image: out of the intermediate arena into the oriented one, where its resample reads)
+        for (size_t k = 0; k < o.or_ids.size(); k++) {
+            const uint32_t i = o.or_ids[k];
+            o.or_jobs[k].src = o.d_pix + o.pix_off[i], o.or_jobs[k].dst = o.d_or + o.or_off[i];
+            o.jobs[i].src = o.or_jobs[k].dst;
+        }
+        B_HIP(hipMemcpy(o.d_or_jobs, o.or_jobs.data(), o.or_jobs.size() * sizeof(OrientJob), hipMemcpyHostToDevice));
+    }
     if (o.route.warp) rc = upload_warp_jobs(b, stream);  // (the u8 resample of the same arguments writes the warp's source; the warp writes the output)
     if (rc) return rc;
     if (o.route.tensor_jobs()) return upload_tensor_jobs(b, stream);
@@ -211,11 +259,13 @@ int output_bind(jpgpu_batch *b, hipStream_t stream, bool all) {
     return JPGPU_OK;
 }
 
-// On a decode, behind the pixel kernels on `s`: the route's resample launch, the launch of runs beside it, the warp behind them.
+// On a decode, behind the pixel kernels on `s`: the orientation launch, the route's resample launch, the launch of runs beside it, the
+// warp behind them.
 int output_launch(jpgpu_batch *b, hipStream_t s) {
     const OutputStage &o = b->o;
     const uint32_t n = (uint32_t)b->descs.size(), es = o.spec.elem_bytes();
     if (o.spec.tensor && o.tn_sent) B_HIP(hipStreamWaitEvent(s, o.tn_sent, 0));  // (the jobs may have gone up on another stream than this one)
+    if (o.route.orient) B_HIP(launch_orient(o.d_or_jobs, (uint32_t)o.or_jobs.size(), o.or_max_tiles, s));  // (in front of the resample: it reads the oriented arena)
     // (placements: the kernels of placed.hip; a tensor output: the same resample, its vertical pass writes every image's tensor; else
     // every image's pixels — wherever the launches before left them in the intermediate arena)
     switch (o.route.resample) {
@@ -258,6 +308,18 @@ int jpgpu_batch_set_warps(jpgpu_batch *b, const jpgpu_warp *warps) {
                            warps[i].m[0], warps[i].m[1], warps[i].m[2], warps[i].m[3], warps[i].m[4], warps[i].m[5], o.spec.w, o.spec.h);
     for (size_t i = 0; i < o.m.size(); i++) o.m[i] = warps ? warps[i] : kIdentity;
     o.wp_dirty = true;
+    return JPGPU_OK;
+}
+int jpgpu_oriented_window(uint32_t orientation, uint32_t w, uint32_t h, const jpgpu_window *oriented, uint32_t *oriented_w, uint32_t *oriented_h,
+                          jpgpu_window *source) {
+    if (!orient_valid(orientation) || w == 0 || h == 0 || w > 65535u || h > 65535u) return JPGPU_ERR_FORMAT;
+    uint32_t ow, oh, sx, sy, sw, sh;
+    oriented_size(orientation, w, h, ow, oh);
+    if (oriented_w) *oriented_w = ow;
+    if (oriented_h) *oriented_h = oh;
+    const jpgpu_window wn = oriented ? *oriented : jpgpu_window{0, 0, 0, 0};
+    if (!orient_source_window(orientation, w, h, wn.x, wn.y, wn.w, wn.h, sx, sy, sw, sh)) return JPGPU_ERR_FORMAT;
+    if (source) *source = jpgpu_window{(uint16_t)sx, (uint16_t)sy, (uint16_t)sw, (uint16_t)sh};
     return JPGPU_OK;
 }
 int jpgpu_warp_check(const jpgpu_warp *warp, uint32_t out_w, uint32_t out_h) {

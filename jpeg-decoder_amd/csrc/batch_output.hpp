@@ -5,6 +5,7 @@
 #include <string.h>
 
 #include "batch_layout.hpp"
+#include "orient_band.hpp"
 #include "placed_band.hpp"
 #include "resample_band.hpp"
 #include "tensor_band.hpp"
@@ -22,6 +23,7 @@ struct OutputSpec {
     uint8_t fill[4] = {0, 0, 0, 0};     // what a placement leaves uncovered
     bool warp = false;                  // warp options ...
     jpgpu_warp_options wp{};            // ... and which
+    bool orient = false;                // some image has an EXIF orientation other than 1 (jpgpu_batch_create_oriented)
     bool sized() const { return w != 0 || h != 0; }
     uint32_t elem_bytes() const { return tensor ? tensor_elem_bytes(tn.dtype) : 1u; }
     uint32_t channels(uint32_t ncomp) const { return rgb ? 3u : ncomp; }
@@ -30,7 +32,7 @@ inline bool operator==(const OutputSpec &a, const OutputSpec &b) {
     return a.w == b.w && a.h == b.h && a.filter == b.filter && a.rgb == b.rgb && a.tensor == b.tensor && a.tn.dtype == b.tn.dtype &&
            a.tn.reserved == b.tn.reserved && memcmp(a.tn.mean, b.tn.mean, sizeof a.tn.mean) == 0 && memcmp(a.tn.std, b.tn.std, sizeof a.tn.std) == 0 &&
            memcmp(a.fill, b.fill, 4) == 0 && a.warp == b.warp && a.wp.filter == b.wp.filter && memcmp(a.wp.fill, b.wp.fill, 4) == 0 &&
-           a.wp.reserved == b.wp.reserved;
+           a.wp.reserved == b.wp.reserved && a.orient == b.orient;
 }
 inline uint32_t pack_fill(const uint8_t f[4]) { return (uint32_t)f[0] | ((uint32_t)f[1] << 8) | ((uint32_t)f[2] << 16) | ((uint32_t)f[3] << 24); }
 
@@ -44,6 +46,7 @@ inline int output_rule(const OutputSpec &s, std::string &why) {
     if (s.filter >= RS_FILTERS) return no(JPGPU_ERR_FORMAT, "resample filter %u: the ids are 0..%u (JPGPU_FILTER_*)", s.filter, RS_FILTERS - 1u);
     if (s.filter && !s.sized()) return why = std::string("a resample filter (") + resample_filter_name(s.filter) + ") needs an output size", JPGPU_ERR_UNSUPPORTED;
     if (s.rgb && !s.sized()) return why = "RGB output (JPGPU_BATCH_RGB_OUTPUT) needs an output size", JPGPU_ERR_UNSUPPORTED;
+    if (s.orient && !s.sized()) return why = "EXIF orientations need an output size", JPGPU_ERR_UNSUPPORTED;
     if (s.warp && !s.sized()) return why = "a warp needs an output size", JPGPU_ERR_FORMAT;
     if (s.warp && (s.wp.filter > WP_BILINEAR || s.wp.reserved != 0))
         return no(JPGPU_ERR_FORMAT, "warp options: filter %u, reserved %u (JPGPU_WARP_NEAREST or JPGPU_WARP_BILINEAR, reserved 0)", s.wp.filter, s.wp.reserved);
@@ -81,6 +84,30 @@ inline uint32_t normalise_placements(const jpgpu_placement *pls, uint32_t n, uin
     return n;
 }
 
+// The orientations of a call (NULL: none) against the rule: n, or the index of the first value outside 1..8; `any`: one is not 1.
+inline uint32_t check_orientations(const uint8_t *o, uint32_t n, bool &any) {
+    any = false;
+    for (uint32_t i = 0; o && i < n; i++) {
+        if (!orient_valid(o[i])) return i;
+        any = any || o[i] != 1u;
+    }
+    return n;
+}
+// The window `wn` of image d's ORIENTED output under orientation o, as the window of its output that the pixel routes decode.
+// JPGPU_ERR_FORMAT with the reason in `why` for one outside the oriented image.
+inline int orient_window_rule(const jpgpu_image_desc &d, uint32_t o, jpgpu_window &wn, std::string &why) {
+    uint32_t gw = 0, gh = 0, sx, sy, sw, sh;
+    window_grid(d.components, d.ncomp, d.out_w, d.out_h, gw, gh);
+    if (!orient_source_window(o, gw, gh, wn.x, wn.y, wn.w, wn.h, sx, sy, sw, sh)) {
+        char msg[200];
+        snprintf(msg, sizeof msg, "window (%u, %u) %ux%u outside the oriented %ux%u image (orientation %u)", wn.x, wn.y, wn.w, wn.h, orient_swaps(o) ? gh : gw,
+                 orient_swaps(o) ? gw : gh, o);
+        return why = msg, JPGPU_ERR_FORMAT;
+    }
+    wn = jpgpu_window{(uint16_t)sx, (uint16_t)sy, (uint16_t)sw, (uint16_t)sh};
+    return JPGPU_OK;
+}
+
 // Bytes of one image of `ncomp` components in the output arena, or (`u8`) in the arena a warp reads: what the u8 batch's output would be.
 inline size_t output_image_bytes(const OutputSpec &s, uint32_t ncomp, bool u8 = false) {
     return (size_t)s.w * s.h * s.channels(ncomp) * (u8 ? 1u : s.elem_bytes());
@@ -92,18 +119,18 @@ inline size_t output_arena(const OutputSpec &s, const std::vector<jpgpu_image_de
     return arena_layout(lens, off, len);
 }
 
-// The route: which resample launch runs, whether the launch of runs of bands goes beside it, whether a warp follows.  Allocation, job
-// upload and launch switch on it.
+// The route: whether the orientation launch runs in front, which resample launch runs, whether the launch of runs of bands goes beside
+// it, whether a warp follows.  Allocation, job upload and launch switch on it.
 enum class Resample : uint8_t { None, Band, Tensor, Placed, PlacedTensor };
 struct OutputRoute {
     Resample resample = Resample::None;
-    bool runs = false, warp = false;
+    bool orient = false, runs = false, warp = false;
     bool tensor_jobs() const { return resample == Resample::Tensor || resample == Resample::PlacedTensor; }
 };
 inline OutputRoute output_route(const OutputSpec &s, bool placed, uint32_t max_runs) {
     OutputRoute r;
     if (!s.sized()) return r;
-    r.warp = s.warp;
+    r.warp = s.warp, r.orient = s.orient;
     const bool tensor = s.tensor && !s.warp;  // (a warped batch resamples to u8, whatever it writes in the end)
     r.resample = placed ? (tensor ? Resample::PlacedTensor : Resample::Placed) : (tensor ? Resample::Tensor : Resample::Band);
     r.runs = max_runs != 0 && !placed;

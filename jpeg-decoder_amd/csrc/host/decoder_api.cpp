@@ -11,6 +11,7 @@
 #include <vector>
 
 #include "../host_common.hpp"
+#include "exif.hpp"
 #include "frontend.hpp"
 
 using jpgpu::host::DecodeError;
@@ -520,6 +521,7 @@ const uint8_t *jpgpu_decoder_xmp_data(const jpgpu_decoder *d, size_t *len) {
     if (len) *len = v ? v->size() : 0;
     return v ? v->data() : nullptr;
 }
+uint32_t jpgpu_exif_orientation(const uint8_t *exif, size_t len) { return jpgpu::host::exif_orientation(exif, len); }
 const uint8_t *jpgpu_decoder_icc_profile(jpgpu_decoder *d, size_t *len) {
     if (len) *len = 0;
     if (!d || !d->fe->icc_profile(d->icc)) return nullptr;

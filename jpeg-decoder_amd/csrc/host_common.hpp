@@ -58,10 +58,11 @@ bool batch_image_windowed(const jpgpu_batch *b, uint32_t image);  // ... is this
 int batch_rewindow(jpgpu_batch *b, const jpgpu_window *windows, const jpgpu_placement *placements = nullptr);
 size_t batch_out_arena_bound(const jpgpu_batch *b);  // jpgpu_batch_out_arena_bytes of the same images without windows
 
-// The one creator behind jpgpu_batch_create*: a batch of `spec` (batch_output.hpp), default flags; placements NULL: none
+// The one creator behind jpgpu_batch_create*: a batch of `spec` (batch_output.hpp), default flags; placements NULL: none; orientations
+// NULL: none (jpgpu_batch_create_oriented: the windows are then windows of the oriented images)
 struct OutputSpec;
 int batch_create_with(int device, const jpgpu_image_desc *descs, const jpgpu_window *windows, const jpgpu_placement *placements, uint32_t n_images,
-                      const OutputSpec &spec, jpgpu_batch **out);
+                      const OutputSpec &spec, jpgpu_batch **out, const uint8_t *orientations = nullptr);
 
 // before a worker goes back to the decoder API's pool of idle workers
 void worker_recycle(jpgpu_worker *w);

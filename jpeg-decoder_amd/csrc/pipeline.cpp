@@ -22,6 +22,7 @@
 
 #include "batch_output.hpp"
 #include "compact.hpp"
+#include "host/exif.hpp"
 #include "host/frontend.hpp"
 
 using jpgpu::host::DecodeError;
@@ -259,6 +260,7 @@ struct SubBatch {
     std::vector<uint8_t> flips;       // a tensor batch: the flip of every image as the batch holds it (jpgpu_batch_set_flips)
     std::vector<jpgpu_placement> pls; // a fit: the placement of every image as the batch holds it
     std::vector<jpgpu_warp> warps;    // a warp: the matrix of every image as the batch holds it (jpgpu_batch_set_warps)
+    std::vector<uint8_t> orients;     // the EXIF orientation of every image as the batch was created with it; empty: all ones
     uint32_t remaining = 0;  // images not yet uploaded / failed (uploader thread only)
     hipEvent_t ready[kCopyStreams] = {nullptr, nullptr, nullptr, nullptr};
     hipEvent_t decoded = nullptr;  // recorded on the compute stream behind the sub-batch's pixel kernels: downloads and the gather wait for it
@@ -277,6 +279,7 @@ struct SubBatch {
         flips.clear();
         pls.clear();
         warps.clear();
+        orients.clear();
     }
 };
 
@@ -320,6 +323,8 @@ struct jpgpu_pipeline {
     jpgpu::OutputSpec out;          // jpgpu_pipeline_set_output_size / _tensor_output / _rgb_output / _filter / _warp, and the fit's fill
     jpgpu_fit fit{};                // jpgpu_pipeline_set_fit (zeros — stretch — without one: every placement is the whole output)
     bool fit_on() const { return fit.mode != JPGPU_FIT_STRETCH; }
+    bool exif_orient = false;       // jpgpu_pipeline_set_exif_orientation: every file's EXIF orientation is applied in front of the output size
+    std::vector<uint8_t> orients;   // per image of the last call: the orientation applied (jpgpu_pipeline_image_orientation; 1 when off)
     int color_transform = -1;       // jpgpu_pipeline_set_color_transform (< 0: what every image says itself)
     size_t max_bytes = SIZE_MAX;    // jpgpu_pipeline_set_max_decoding_buffer_size
     uint32_t n_compute = kComputeStreamsDefault;  // streams in use (JPGPU_PIPE_STREAMS: tuning knob, up to kComputeStreams)
@@ -699,10 +704,22 @@ static void read_header(Call &c, uint32_t i) {
         c.cand[i] = d;
         uint32_t gw = 0, gh = 0;
         bool windowed = false;
-        v = jpgpu::batch_check_window(d, c.windows ? c.windows[i] : jpgpu_window{0, 0, 0, 0}, windowed, gw, gh, why);
+        // (the file's EXIF orientation: the window is then one of the ORIENTED image, checked against its size and mapped to the source
+        // window the pixel routes decode; windows and fits below are resolved against the oriented size)
+        const jpgpu_window given = c.windows ? c.windows[i] : jpgpu_window{0, 0, 0, 0};
+        jpgpu_window source = given;
+        uint32_t o = 1;
+        if (p->exif_orient) {
+            const std::vector<uint8_t> *exif = fe.exif();
+            o = exif ? jpgpu::host::exif_orientation(exif->data(), exif->size()) : 1u;
+            p->orients[i] = (uint8_t)o;
+            v = o != 1u ? jpgpu::orient_window_rule(d, o, source, why) : JPGPU_OK;
+            if (v != JPGPU_OK) throw DecodeError{v, why};
+        }
+        v = jpgpu::batch_check_window(d, source, windowed, gw, gh, why);
         if (v != JPGPU_OK) throw DecodeError{v, why};
-        p->wins[i] = jpgpu_window{0, 0, (uint16_t)gw, (uint16_t)gh};
-        if (windowed) c.win[i] = p->wins[i] = c.windows[i];
+        p->wins[i] = jpgpu_window{0, 0, (uint16_t)(jpgpu::orient_swaps(o) ? gh : gw), (uint16_t)(jpgpu::orient_swaps(o) ? gw : gh)};
+        if (windowed) c.win[i] = p->wins[i] = given;  // (as given: the batch maps it again)
         // (the output options against THIS image — planar output has no resample, the tensor format's means and stds are checked for
         // its channels: the image fails alone, like a refused window)
         v = jpgpu::output_image_rule(p->out, d.ncomp, probe.color_fn, why);
@@ -810,7 +827,9 @@ static int prepare_sub_batch(Call &c, uint32_t j) {
     std::vector<uint8_t> fl;         // a tensor output: every image's flip
     std::vector<jpgpu_placement> pls;  // a fit: every image's placement
     std::vector<jpgpu_warp> wm;        // a warp: every image's matrix
-    bool sub_windowed = false;
+    std::vector<uint8_t> ors;          // EXIF orientations: every image's (left empty when all are 1: the batch without the argument)
+    bool sub_windowed = false, sub_oriented = false;
+    for (uint32_t k = first; p->exif_orient && k < last; k++) sub_oriented = sub_oriented || p->orients[ok[k]] != 1;
     for (uint32_t k = first; c.any_window && k < last; k++) sub_windowed = sub_windowed || c.win[ok[k]].w != 0;
     for (uint32_t k = first; k < last; k++) {
         p->sub_of[ok[k]] = (int32_t)j;
@@ -820,6 +839,7 @@ static int prepare_sub_batch(Call &c, uint32_t j) {
         if (p->out.tensor) fl.push_back(c.flips && c.flips[ok[k]] ? 1 : 0);
         if (p->fit_on()) pls.push_back(p->places[ok[k]]);
         if (p->out.warp) wm.push_back(c.warps ? c.warps[ok[k]] : jpgpu_warp{{1.0, 0.0, 0.0, 0.0, 1.0, 0.0}});
+        if (sub_oriented) ors.push_back(p->orients[ok[k]]);
     }
     sb.remaining = last - first;
     // Sub-batches of device-entropy images need no pinned staging for coefficients (their entropy-coded bytes are staged by
@@ -829,7 +849,8 @@ static int prepare_sub_batch(Call &c, uint32_t j) {
     // (other output options — another size, format, filter, fill or warp stage — or another fit rule: other tables, arenas and
     // launches for the batch's lifetime, the sub-batch is created anew)
     bool reuse = sb.batch && descs.size() == sb.descs.size() && sb.compact == c.compact && (sb.h_coef != nullptr) == staged && sb.made_with == p->out &&
-                 sb.fit.mode == p->fit.mode && sb.fit.size == p->fit.size;
+                 sb.fit.mode == p->fit.mode && sb.fit.size == p->fit.size &&
+                 sb.orients == ors;  // (other orientations: another arena layout, other jobs and resample tables — never a kept batch's)
     const bool same_pls = pls.size() == sb.pls.size() && (pls.empty() || memcmp(pls.data(), sb.pls.data(), pls.size() * sizeof(jpgpu_placement)) == 0);
     for (size_t k = 0; reuse && k < descs.size(); k++) reuse = same_geometry(descs[k], sb.descs[k]);
     // ... and the same windows: the window group's geometry and the output offsets are made from them (a kept batch with other
@@ -850,7 +871,8 @@ static int prepare_sub_batch(Call &c, uint32_t j) {
     int rc = JPGPU_OK;
     if (!reuse) {
         sb.drop();
-        rc = jpgpu::batch_create_with(p->device, descs.data(), wins.empty() ? nullptr : wins.data(), p->fit_on() ? pls.data() : nullptr, (uint32_t)descs.size(), p->out, &sb.batch);
+        rc = jpgpu::batch_create_with(p->device, descs.data(), wins.empty() ? nullptr : wins.data(), p->fit_on() ? pls.data() : nullptr, (uint32_t)descs.size(), p->out, &sb.batch,
+                                      ors.empty() ? nullptr : ors.data());
         if (rc) {
             // a frame the pixel backend refuses (e.g. an impossible sampling combination) fails the images of
             // its sub-batch the way the reference fails it in compute_image
@@ -866,7 +888,7 @@ static int prepare_sub_batch(Call &c, uint32_t j) {
         }
         sb.descs = descs;
         sb.wins = wins;
-        sb.made_with = p->out, sb.fit = p->fit, sb.pls = pls;
+        sb.made_with = p->out, sb.fit = p->fit, sb.pls = pls, sb.orients = ors;
         sb.flips.assign(descs.size(), 0);
         sb.warps.assign(p->out.warp ? descs.size() : 0, jpgpu_warp{{1.0, 0.0, 0.0, 0.0, 1.0, 0.0}});
         sb.compact = c.compact;
@@ -1323,6 +1345,8 @@ int jpgpu_pipeline_decode_warped(jpgpu_pipeline *p, const uint8_t *const *data, 
     if (p && p->fit_on() && !p->out.w) return jpgpu::set_err(p->err, JPGPU_ERR_FORMAT, "jpgpu_pipeline_decode: a fit needs an output size (jpgpu_pipeline_set_output_size)");
     if (p && flips && !p->out.tensor) return jpgpu::set_err(p->err, JPGPU_ERR_FORMAT, "jpgpu_pipeline_decode_augmented: flips need a tensor output (jpgpu_pipeline_set_tensor_output)");
     if (p && warps && !p->out.warp) return jpgpu::set_err(p->err, JPGPU_ERR_FORMAT, "jpgpu_pipeline_decode_warped: warps need warp options (jpgpu_pipeline_set_warp)");
+    if (p && p->exif_orient && !p->out.w)
+        return jpgpu::set_err(p->err, JPGPU_ERR_FORMAT, "jpgpu_pipeline_decode: EXIF orientation needs an output size (jpgpu_pipeline_set_output_size)");
     if (p && !p->children.empty()) return (n && (!data || !len)) ? JPGPU_ERR_FORMAT : multi_decode(p, data, len, windows, flips, warps, n, flags);
     if (!p || !p->pool || (n && (!data || !len))) return JPGPU_ERR_FORMAT;
     if ((flags & JPGPU_PIPELINE_GATHER) && !p->gather_on) flags &= ~(uint32_t)JPGPU_PIPELINE_GATHER;  // (one device: the pixels are where a gather would put them)
@@ -1341,6 +1365,7 @@ int jpgpu_pipeline_decode_warped(jpgpu_pipeline *p, const uint8_t *const *data, 
     p->infos.assign(n, jpgpu_image_info{});
     p->wins.assign(n, jpgpu_window{0, 0, 0, 0});
     p->places.assign(n, jpgpu_placement{0, 0, 0, 0});
+    p->orients.assign(n, 1);
     p->sub_of.assign(n, -1);
     p->plans.assign(n, {});
     p->prog_plans.assign(n, {});
@@ -1539,6 +1564,16 @@ int jpgpu_pipeline_set_rgb_output(jpgpu_pipeline *p, int on) {
     for (jpgpu_pipeline *c : p->children) jpgpu_pipeline_set_rgb_output(c, on);
     p->out.rgb = on != 0;
     return JPGPU_OK;
+}
+int jpgpu_pipeline_set_exif_orientation(jpgpu_pipeline *p, int on) {
+    if (!p) return JPGPU_ERR_FORMAT;
+    for (jpgpu_pipeline *c : p->children) jpgpu_pipeline_set_exif_orientation(c, on);
+    p->exif_orient = on != 0;
+    return JPGPU_OK;
+}
+int jpgpu_pipeline_image_orientation(const jpgpu_pipeline *p, uint32_t i) {
+    MULTI(p, i, jpgpu_pipeline_image_orientation(c, ci), 1)
+    return (p && i < p->n && i < p->orients.size()) ? p->orients[i] : 1;
 }
 uint32_t jpgpu_pipeline_device_count(const jpgpu_pipeline *p) { return !p ? 0u : (p->children.empty() ? 1u : (uint32_t)p->children.size()); }
 int jpgpu_pipeline_image_device(const jpgpu_pipeline *p, uint32_t i) {

@@ -76,7 +76,7 @@ class Pipeline:
 
     def decode(self, streams, download=True, dense=False, device_entropy=True, scale=None, color_transform=None, max_decoding_buffer_size=None,
                gather=False, host_light=None, input_pinned=False, progressive_on_host=False, windows=None, output_size=None,
-               tensor=None, flips=None, rgb=False, fit=None, filter=None, warp=None, warps=None):
+               tensor=None, flips=None, rgb=False, fit=None, filter=None, warp=None, warps=None, exif_orientation=False):
         """-> list with, per stream, a numpy uint8 array of the decoded pixels (``Decoder.decode()``'s Vec<u8>) or the
         ``Error`` instance that stream produced.  download=False leaves the pixels in HBM (see ``device_pointer``); dense=True sends all
         64 coefficients of every block over PCIe instead of the compact form (same pixels, A/B switch); device_entropy=True
@@ -122,7 +122,11 @@ class Pipeline:
         fillcolor=warp.fill)`` of every stream's u8 result, mirrored first when the stream is flipped.
         warps: None (identities) or a list with six coefficients or None per stream (needs `warp`, else FormatError and nothing is
         decoded); a matrix the library refuses fails its stream alone.  Fresh matrices for the same files keep the pipeline's
-        sub-batches, like windows and flips."""
+        sub-batches, like windows and flips.
+        exif_orientation: True (jpgpu_pipeline_set_exif_orientation, set on every call; needs output_size, else FormatError and nothing
+        is decoded): every stream is oriented by its EXIF orientation tag in front of the output size — ``ImageOps.exif_transpose`` —
+        and `windows` and `fit` are meant on the oriented image.  ``orientation(i)`` gives the value applied (1 for a
+        file without the tag or with damaged EXIF), ``window(i)`` the window in oriented coordinates, ``info(i)`` keeps the file's size."""
         if isinstance(streams, PinnedFiles):
             bufs = None
             n = len(streams)
@@ -147,6 +151,7 @@ class Pipeline:
         st = L.jpgpu_pipeline_set_tensor_output(self._h, None if fmt is None else C.byref(fmt))
         check(st, L.jpgpu_pipeline_last_error(self._h) if st else b"")
         check(L.jpgpu_pipeline_set_rgb_output(self._h, 1 if rgb else 0), b"set_rgb_output")
+        check(L.jpgpu_pipeline_set_exif_orientation(self._h, 1 if exif_orientation else 0), b"set_exif_orientation")
         st = L.jpgpu_pipeline_set_filter(self._h, filt)
         check(st, L.jpgpu_pipeline_last_error(self._h) if st else b"")
         fit_s = None if fit is None else fit.struct()
@@ -209,6 +214,10 @@ class Pipeline:
         if N.lib().jpgpu_pipeline_image_placement(self._h, image, C.byref(pl)):
             return None
         return pl.rw, pl.rh, pl.x, pl.y
+
+    def orientation(self, image):
+        """jpgpu_pipeline_image_orientation: the EXIF orientation (1..8) applied to the image of the last call; 1 with the option off."""
+        return int(N.lib().jpgpu_pipeline_image_orientation(self._h, image))
 
     def window(self, image):
         """jpgpu_pipeline_image_window: (x, y, w, h) the image of the last call was decoded with — (0, 0, W, H) of its output grid
