@@ -416,6 +416,73 @@ int jpgpu_batch_create_oriented(int device, const jpgpu_image_desc *descs, const
 int jpgpu_oriented_window(uint32_t orientation, uint32_t w, uint32_t h, const jpgpu_window *oriented, uint32_t *oriented_w, uint32_t *oriented_h,
                           jpgpu_window *source);
 uint32_t jpgpu_exif_orientation(const uint8_t *exif, size_t len);
+/* ---- Colour operations behind the fixed output size: a program of Pillow operations per image ---------------------
+ * jpgpu_batch_create_oriented with a colour stage behind the resample.  With R the image's u8 result of out_w x out_h, exactly as the
+ * same batch without colour defines it (RGB conversion, orientation, resample and placement fill included), and a program of n <= 4
+ * operations per image:
+ *     C             = op_{n-1}( ... op_1( op_0( R ) ) )                     n == 0: C = R
+ *     out(Y, X, c)  = Warp_i( F ? mirror_columns(C) : C )(Y, X, c)          warp and flip as above; absent: the identity
+ *     elem(c, Y, X) = T[c][ out(Y, X, c) ]                                  tensor batches
+ * Colour comes BEFORE the warp (a warp's fill is not recoloured); a placement's fill is part of R, is seen by the statistics and is
+ * recoloured, as Pillow does on the pasted canvas.  Each operation works on the current image P (u8, H x W x 3); statistics are those of
+ * the current P:
+ *     0 IDENTITY      -            P
+ *     1 BRIGHTNESS    factor f     blend(0, p, f) per channel value                      ImageEnhance.Brightness(P).enhance(f)
+ *     2 CONTRAST      f            blend(m, p, f), m the image's mean                    ImageEnhance.Contrast(P).enhance(f)
+ *     3 COLOR         f            blend(L(px), p, f) per pixel (f = 0: grayscale)       ImageEnhance.Color(P).enhance(f)
+ *     4 SOLARIZE      threshold t  p < t ? p : 255 - p          t an integer 0..256      ImageOps.solarize(P, t)
+ *     5 POSTERIZE     bits b       p & ~(2^(8-b) - 1)           b an integer 1..8        ImageOps.posterize(P, b)
+ *     6 INVERT        -            255 - p                                               ImageOps.invert(P)
+ *     7 AUTOCONTRAST  -            per channel                                           ImageOps.autocontrast(P)   (cutoff 0)
+ *     8 EQUALIZE      -            per channel                                           ImageOps.equalize(P)
+ *   blend(a, b, f): IEEE float32, the product and the sum rounded once each, no fused multiply-add: t = (float)a + f * (float)(b - a);
+ *     0 <= f <= 1: (uint8)(int)t (truncated); otherwise t <= 0: 0, t >= 255: 255, else (uint8)(int)t.
+ *   L(px) = (R 19595 + G 38470 + B 7471 + 0x8000) >> 16.   m = (2 s + n) / (2 n) in integers, s the sum of L over the n = W H pixels.
+ *   AUTOCONTRAST, per channel: lo / hi the least / greatest value present; hi <= lo: identity; else in IEEE double, every operation
+ *     rounded once: scale = 255.0 / (hi - lo), offset = -lo * scale, lut[i] = clamp((int)(i * scale + offset), 0, 255), truncated.
+ *   EQUALIZE, per channel with histogram h: nz the non-zero counts; fewer than two: identity; step = (sum(nz) - nz[last]) / 255;
+ *     step == 0: identity; else acc = step / 2; for i = 0..255: lut[i] = min(acc / step, 255), then acc += h[i].
+ * Only images whose output has three channels take a non-empty program (RGB / YCbCr sources, or any source under
+ * JPGPU_BATCH_RGB_OUTPUT): another one is JPGPU_ERR_UNSUPPORTED.  A program is refused (jpgpu_colour_check: JPGPU_ERR_FORMAT) for
+ * n > 4, an unknown operation, a factor that is not finite, negative or above 256, a SOLARIZE value that is no integer in 0..256, a
+ * POSTERIZE value that is no integer in 1..8.
+ * `colour` NULL IS jpgpu_batch_create_oriented: same kernels, launches, bytes and path.  Otherwise every image starts with the empty
+ * program; the batch's resample launch is the u8 one of the same arguments and writes the arena a warp reads, one launch behind it
+ * (a workgroup per image) runs the programs there in place, and the batch's warp launch — with identity matrices in a batch without
+ * warp options — writes the output arena.  jpgpu_batch_path gains "+colour" in front of "+warp..." / "+tensor".  Colour without an
+ * output size: JPGPU_ERR_UNSUPPORTED, as RGB output; reserved != 0: JPGPU_ERR_FORMAT. */
+enum {
+    JPGPU_COLOUR_IDENTITY = 0, JPGPU_COLOUR_BRIGHTNESS = 1, JPGPU_COLOUR_CONTRAST = 2, JPGPU_COLOUR_COLOR = 3, JPGPU_COLOUR_SOLARIZE = 4,
+    JPGPU_COLOUR_POSTERIZE = 5, JPGPU_COLOUR_INVERT = 6, JPGPU_COLOUR_AUTOCONTRAST = 7, JPGPU_COLOUR_EQUALIZE = 8
+};
+typedef struct jpgpu_colour_op {
+    uint32_t op; /* JPGPU_COLOUR_* */
+    float value;
+} jpgpu_colour_op;
+typedef struct jpgpu_colour_program {
+    uint32_t n; /* 0..4 */
+    jpgpu_colour_op ops[4];
+} jpgpu_colour_program;
+typedef struct jpgpu_colour_options {
+    uint32_t reserved; /* 0 */
+} jpgpu_colour_options;
+int jpgpu_batch_create_coloured(int device, const jpgpu_image_desc *descs, const jpgpu_window *windows, const jpgpu_placement *placements,
+                                const uint8_t *fill, uint16_t out_w, uint16_t out_h, const jpgpu_tensor_format *format,
+                                const jpgpu_warp_options *warp, const uint8_t *orientations, const jpgpu_colour_options *colour, uint32_t n_images,
+                                uint32_t flags, jpgpu_batch **out);
+/* The program of every image (`programs`: n_images entries; NULL: empty programs) from the next jpgpu_batch_decode enqueued on: built
+ * into the images' job records, sent with them on the decode's stream (a decode already enqueued keeps its programs).  One refused
+ * program refuses the call — JPGPU_ERR_FORMAT, or JPGPU_ERR_UNSUPPORTED for a non-empty program on an image without three output
+ * channels — and nothing is changed.  JPGPU_ERR_UNSUPPORTED on a batch without colour. */
+int jpgpu_batch_set_colour_programs(jpgpu_batch *b, const jpgpu_colour_program *programs);
+/* Pure host functions (no device needed; the device runs the same bodies).  jpgpu_colour_check: the refusal rule above (JPGPU_OK /
+ * JPGPU_ERR_FORMAT).  jpgpu_colour_point_lut: the 256-entry table of BRIGHTNESS, CONTRAST (with the image's mean `mean`, 0..255),
+ * SOLARIZE, POSTERIZE, INVERT or IDENTITY; another operation or a refused value: JPGPU_ERR_FORMAT.  jpgpu_colour_autocontrast_lut /
+ * jpgpu_colour_equalize_lut: one channel's table from its histogram h[256]. */
+int jpgpu_colour_check(const jpgpu_colour_program *program);
+int jpgpu_colour_point_lut(uint32_t op, float value, uint32_t mean, uint8_t *lut);
+int jpgpu_colour_autocontrast_lut(const uint32_t *h, uint8_t *lut);
+int jpgpu_colour_equalize_lut(const uint32_t *h, uint8_t *lut);
 void jpgpu_batch_destroy(jpgpu_batch *b);
 const char *jpgpu_batch_last_error(const jpgpu_batch *b);
 

@@ -283,6 +283,12 @@ int jpgpu_pipeline_set_fit(jpgpu_pipeline *p, const jpgpu_fit *fit);
  * anything is decoded.  Changed options create the kept sub-batches anew.  Composes with the scale, windows, the filter, a fit, RGB
  * output, the tensor format and flips.  An unknown filter or reserved != 0: JPGPU_ERR_FORMAT, nothing changes. */
 int jpgpu_pipeline_set_warp(jpgpu_pipeline *p, const jpgpu_warp_options *warp);
+/* A colour stage behind the output size for every image of the calls that follow (sticky; NULL: off — the routes, launches and bytes
+ * without it): the sub-batches are created with jpgpu_batch_create_coloured (jpgpu.h: a program of Pillow colour operations on every
+ * image's u8 result, before the warp and the tensor table); the programs come per call with
+ * jpgpu_pipeline_decode_coloured.  Colour needs an output size: without one the next decode fails whole with JPGPU_ERR_FORMAT before
+ * anything is decoded.  Switching it on or off creates the kept sub-batches anew.  reserved != 0: JPGPU_ERR_FORMAT, nothing changes. */
+int jpgpu_pipeline_set_colour(jpgpu_pipeline *p, const jpgpu_colour_options *colour);
 /* The placement image `image` of the last call was decoded with: jpgpu_fit_placement of its source size, (out_w, out_h, 0, 0) without a
  * fit.  JPGPU_ERR_FORMAT without an output size, for an image without a frame, or one whose window or rule was refused. */
 int jpgpu_pipeline_image_placement(const jpgpu_pipeline *p, uint32_t image, jpgpu_placement *out);
@@ -325,6 +331,15 @@ int jpgpu_pipeline_decode_augmented(jpgpu_pipeline *p, const uint8_t *const *dat
  * the flips. */
 int jpgpu_pipeline_decode_warped(jpgpu_pipeline *p, const uint8_t *const *data, const size_t *len, const jpgpu_window *windows,
                                  const uint8_t *flips, const jpgpu_warp *warps, uint32_t n_images, uint32_t flags);
+/* jpgpu_pipeline_decode_warped with a colour program per image (`programs`: n_images entries; NULL with jpgpu_pipeline_set_colour in
+ * force: empty programs; NULL without: exactly jpgpu_pipeline_decode_warped).  `programs` without colour options fails the call with
+ * JPGPU_ERR_FORMAT before anything is decoded.  A program jpgpu_colour_check refuses gives THAT image JPGPU_ERR_FORMAT, a non-empty one
+ * for an image without three output channels (a gray or CMYK file without RGB output) JPGPU_ERR_UNSUPPORTED; every other image of the
+ * call is decoded.  Fresh programs never create a kept sub-batch anew: they are set in place (jpgpu_batch_set_colour_programs), like the
+ * matrices. */
+int jpgpu_pipeline_decode_coloured(jpgpu_pipeline *p, const uint8_t *const *data, const size_t *len, const jpgpu_window *windows,
+                                   const uint8_t *flips, const jpgpu_warp *warps, const jpgpu_colour_program *programs, uint32_t n_images,
+                                   uint32_t flags);
 /* The window image i of the last call was decoded with: what the caller passed, or 0, 0, W, H of the output grid when it had none
  * (JPGPU_ERR_FORMAT for an image without a frame or whose window was refused). */
 int jpgpu_pipeline_image_window(const jpgpu_pipeline *p, uint32_t image, jpgpu_window *out);

@@ -104,6 +104,21 @@ class WarpOptionsStruct(C.Structure):
     _fields_ = [("filter", C.c_uint32), ("fill", C.c_uint8 * 4), ("reserved", C.c_uint32)]
 
 
+class ColourOp(C.Structure):
+    """jpgpu_colour_op: op (JPGPU_COLOUR_*), value."""
+    _fields_ = [("op", C.c_uint32), ("value", C.c_float)]
+
+
+class ColourProgram(C.Structure):
+    """jpgpu_colour_program: n operations (0..4)."""
+    _fields_ = [("n", C.c_uint32), ("ops", ColourOp * 4)]
+
+
+class ColourOptionsStruct(C.Structure):
+    """jpgpu_colour_options: reserved = 0."""
+    _fields_ = [("reserved", C.c_uint32)]
+
+
 class FitStruct(C.Structure):
     """jpgpu_fit: mode (FIT_*), size (shorter side of FIT_SHORTER_SIDE_CROP), fill[4], reserved = 0."""
     _fields_ = [("mode", C.c_uint32), ("size", C.c_uint32), ("fill", C.c_uint8 * 4), ("reserved", C.c_uint32)]
@@ -176,6 +191,14 @@ _PROTOS = {
     "jpgpu_batch_set_warps": (C.c_int, [C.c_void_p, C.POINTER(Warp)]),
     "jpgpu_batch_create_oriented": (C.c_int, [C.c_int, C.POINTER(ImageDesc), C.POINTER(Window), C.POINTER(Placement), C.c_void_p, C.c_uint16, C.c_uint16,
                                               C.POINTER(TensorFormatStruct), C.POINTER(WarpOptionsStruct), C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(C.c_void_p)]),
+    "jpgpu_batch_create_coloured": (C.c_int, [C.c_int, C.POINTER(ImageDesc), C.POINTER(Window), C.POINTER(Placement), C.c_void_p, C.c_uint16, C.c_uint16,
+                                              C.POINTER(TensorFormatStruct), C.POINTER(WarpOptionsStruct), C.c_void_p, C.POINTER(ColourOptionsStruct), C.c_uint32, C.c_uint32,
+                                              C.POINTER(C.c_void_p)]),
+    "jpgpu_batch_set_colour_programs": (C.c_int, [C.c_void_p, C.POINTER(ColourProgram)]),
+    "jpgpu_colour_check": (C.c_int, [C.POINTER(ColourProgram)]),
+    "jpgpu_colour_point_lut": (C.c_int, [C.c_uint32, C.c_float, C.c_uint32, C.c_void_p]),
+    "jpgpu_colour_autocontrast_lut": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "jpgpu_colour_equalize_lut": (C.c_int, [C.c_void_p, C.c_void_p]),
     "jpgpu_oriented_window": (C.c_int, [C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(Window), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(Window)]),
     "jpgpu_exif_orientation": (C.c_uint32, [C.c_void_p, C.c_size_t]),
     "jpgpu_warp_check": (C.c_int, [C.POINTER(Warp), C.c_uint32, C.c_uint32]),
@@ -258,6 +281,9 @@ _PROTOS = {
     "jpgpu_pipeline_set_tensor_output": (C.c_int, [C.c_void_p, C.POINTER(TensorFormatStruct)]),
     "jpgpu_pipeline_set_rgb_output": (C.c_int, [C.c_void_p, C.c_int]),
     "jpgpu_pipeline_set_filter": (C.c_int, [C.c_void_p, C.c_uint32]),
+    "jpgpu_pipeline_set_colour": (C.c_int, [C.c_void_p, C.POINTER(ColourOptionsStruct)]),
+    "jpgpu_pipeline_decode_coloured": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), C.POINTER(Window), C.c_void_p, C.POINTER(Warp),
+                                                 C.POINTER(ColourProgram), C.c_uint32, C.c_uint32]),
     "jpgpu_pipeline_set_exif_orientation": (C.c_int, [C.c_void_p, C.c_int]),
     "jpgpu_pipeline_image_orientation": (C.c_int, [C.c_void_p, C.c_uint32]),
     "jpgpu_pipeline_set_fit": (C.c_int, [C.c_void_p, C.POINTER(FitStruct)]),

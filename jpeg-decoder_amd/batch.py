@@ -5,6 +5,7 @@ import math
 import numpy as np
 
 from . import _native as N
+from .colour import program_structs
 from .error import check
 from .worker import color_transform_id
 
@@ -350,10 +351,17 @@ class Batch:
     UnsupportedError).  Every image is oriented first — ``ImageOps.exif_transpose`` — and everything above is meant on the oriented image:
     the window lies in it and is checked against its size (``oriented_size``), placements are those of the oriented window, and the
     resample's horizontal pass runs on its rows.  `path` gains "+orient" in front; all ones is the batch without the
-    argument.  A value outside 1..8 is a FormatError."""
+    argument.  A value outside 1..8 is a FormatError.
+
+    colour: None / False, or True (jpgpu_batch_create_coloured; needs an output_size, else UnsupportedError).  Every image's u8 result of
+    the above — RGB conversion, orientation, resample and placement fill included — then goes through a program of at most four Pillow
+    colour operations, before the warp and the tensor table (the helpers of ``colour.py``: brightness, contrast,
+    saturation, solarize, posterize, invert, autocontrast, equalize).  Every image starts with the empty program;
+    ``set_colour([...])`` sets the programs from the next decode on.  Only images with three output channels take a non-empty
+    program.  `path` gains "+colour" before "+warp" / "+tensor"."""
 
     def __init__(self, descs, device=0, flags=N.BATCH_DEFAULT, windows=None, output_size=None, tensor=None, rgb=False, placements=None, fill=None,
-                 filter=None, warp=None, orientations=None):
+                 filter=None, warp=None, orientations=None, colour=None):
         self._h = C.c_void_p()
         arr = (N.ImageDesc * len(descs))(*descs)
         wins = window_structs(windows, len(descs))
@@ -370,7 +378,15 @@ class Batch:
         self.warp = warp
         ors = orientation_bytes(orientations, len(descs))
         self.orientations = None if ors is None else list(ors)[: len(descs)]
-        if ors is not None and (self.output_size is not None or any(v != 1 for v in self.orientations)):  # (all ones without a size: no argument)
+        self.colour = bool(colour)
+        if self.colour:
+            w, h = self.output_size if self.output_size is not None else (0, 0)
+            fmt = tensor.struct() if tensor is not None else None
+            wo = warp.struct() if warp is not None else None
+            co = N.ColourOptionsStruct(0)
+            st = N.lib().jpgpu_batch_create_coloured(device, arr, wins, pls, (C.c_uint8 * 4)(*self.fill), w, h, C.byref(fmt) if fmt is not None else None,
+                                                     C.byref(wo) if wo is not None else None, ors, C.byref(co), len(descs), flags, C.byref(self._h))
+        elif ors is not None and (self.output_size is not None or any(v != 1 for v in self.orientations)):  # (all ones without a size: no argument)
             w, h = self.output_size if self.output_size is not None else (0, 0)
             fmt = tensor.struct() if tensor is not None else None
             wo = warp.struct() if warp is not None else None
@@ -512,6 +528,14 @@ class Batch:
         next decode on.  One refused matrix raises FormatError and changes nothing; a batch without `warp` raises UnsupportedError."""
         arr = warp_structs(warps, self.n_images)
         self._check(N.lib().jpgpu_batch_set_warps(self._h, arr))
+
+    def set_colour(self, programs):
+        """jpgpu_batch_set_colour_programs: a program (a list of at most four ``(name, value)`` pairs, or None: the empty one) per image,
+        None for empty programs throughout; in force from the next decode on.  One refused program raises FormatError — a non-empty one
+        for an image without three output channels UnsupportedError — and changes nothing; a batch without `colour` raises
+        UnsupportedError."""
+        arr = program_structs(programs, self.n_images)
+        self._check(N.lib().jpgpu_batch_set_colour_programs(self._h, arr))
 
     def download(self, image):
         n = self.out_bytes(image)

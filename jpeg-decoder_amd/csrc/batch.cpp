@@ -231,6 +231,7 @@ static int batch_create(int device, const jpgpu_image_desc *descs, const jpgpu_w
     if (b->o.placed) b->path += "+place";
     if (resized) b->path += "+resize";
     if (spec.filter) b->path += std::string(":") + resample_filter_name(spec.filter);
+    if (spec.colour) b->path += "+colour";
     if (spec.warp) b->path += spec.wp.filter == WP_BILINEAR ? "+warp:bilinear" : "+warp";
     if (spec.tensor) b->path += "+tensor";
     rc = output_create(b);  // (what was laid out so far becomes the intermediate arena)
@@ -328,6 +329,23 @@ int jpgpu_batch_create_oriented(int device, const jpgpu_image_desc *descs, const
                                    : warp ? "a warp needs an output size (%ux%u: width and height must be 1..%u)" : kNoSize, out_w, out_h);
     }
     return batch_create(device, descs, windows, placements, n_images, flags, spec_of(flags, out_w, out_h, format, fill, warp), out, orientations);
+}
+int jpgpu_batch_create_coloured(int device, const jpgpu_image_desc *descs, const jpgpu_window *windows, const jpgpu_placement *placements, const uint8_t *fill,
+                                uint16_t out_w, uint16_t out_h, const jpgpu_tensor_format *format, const jpgpu_warp_options *warp, const uint8_t *orientations,
+                                const jpgpu_colour_options *colour, uint32_t n_images, uint32_t flags, jpgpu_batch **out) {
+    if (!colour) return jpgpu_batch_create_oriented(device, descs, windows, placements, fill, out_w, out_h, format, warp, orientations, n_images, flags, out);
+    if (!out) return JPGPU_ERR_FORMAT;
+    if (colour->reserved != 0u) return *out = new jpgpu_batch(), set_err((*out)->err, JPGPU_ERR_FORMAT, "colour options: reserved %u (must be 0)", colour->reserved);
+    OutputSpec s = spec_of(flags, out_w, out_h, format, fill, warp);
+    s.colour = true;
+    if (out_w == 0 || out_h == 0) {  // (colour without an output size: the rule's own refusal, as RGB output)
+        std::string why;
+        OutputSpec none;
+        none.colour = true;
+        *out = new jpgpu_batch();
+        return set_err((*out)->err, output_rule(none, why), "%s", why.c_str());
+    }
+    return batch_create(device, descs, windows, placements, n_images, flags, s, out, orientations);
 }
 void jpgpu_batch_destroy(jpgpu_batch *b) {
     if (!b) return;

@@ -123,13 +123,24 @@ struct OutputStage {
     size_t or_cap = 0;
     OrientJob *d_or_jobs = nullptr;
     uint32_t or_max_tiles = 0;
+    // Colour (route.colour; colour_band.hpp): every image's program (jpgpu_batch_set_colour_programs), built into ColourJobs in a pinned
+    // mirror and sent on the decode's stream like the WarpJobs; the launch rewrites the warp's source arena in place, between the u8
+    // resample and the warp launch.  d_cl_scale: colour_scale_table.
+    std::vector<ColourProgram> programs;
+    ColourJob *d_cl_jobs = nullptr, *h_cl_jobs = nullptr;
+    double *d_cl_scale = nullptr;
+    hipEvent_t cl_sent = nullptr;
+    bool cl_dirty = false;
     void free() {
-        for (void *d : {(void *)d_pix, (void *)d_wsrc, (void *)d_tab, (void *)d_bpr, d_tn_table, d_jobs, (void *)d_wp_jobs, (void *)d_or, (void *)d_or_jobs})
+        for (void *d : {(void *)d_pix, (void *)d_wsrc, (void *)d_tab, (void *)d_bpr, d_tn_table, d_jobs, (void *)d_wp_jobs, (void *)d_or, (void *)d_or_jobs,
+                        (void *)d_cl_jobs, (void *)d_cl_scale})
             if (d) (void)hipFree(d);
         if (h_jobs) (void)hipHostFree(h_jobs);
         if (h_wp_jobs) (void)hipHostFree(h_wp_jobs);
+        if (h_cl_jobs) (void)hipHostFree(h_cl_jobs);
         if (tn_sent) (void)hipEventDestroy(tn_sent);
         if (wp_sent) (void)hipEventDestroy(wp_sent);
+        if (cl_sent) (void)hipEventDestroy(cl_sent);
     }
 };
 // batch_output.cpp, what batch.cpp calls: at creation, on a refresh of the job tables, on a decode behind the pixel kernels, and for

@@ -28,6 +28,15 @@ int output_create(jpgpu_batch *b) {
         B_HIP(hipMalloc((void **)&o.d_wp_jobs, warp_jobs_bytes(b)));
         o.wp_dirty = true;
     }
+    if (o.route.colour) {  // (every image starts with the empty program)
+        double scale[256];
+        colour_scale_table(scale);
+        o.programs.assign(n, ColourProgram{});
+        B_HIP(hipMalloc((void **)&o.d_cl_jobs, (size_t)n * sizeof(ColourJob)));
+        B_HIP(hipMalloc((void **)&o.d_cl_scale, sizeof scale));
+        B_HIP(hipMemcpy(o.d_cl_scale, scale, sizeof scale, hipMemcpyHostToDevice));
+        o.cl_dirty = true;
+    }
     if (o.spec.tensor) {  // (the table of four channels: every image looks up its own first ncomp rows)
         B_HIP(hipMalloc(&o.d_tn_table, TN_TABLE_MAX));
         std::vector<uint32_t> table(TN_TABLE_MAX / 4u, 0u);
@@ -149,7 +158,8 @@ int output_retable(jpgpu_batch *b) {
     o.route = output_route(o.spec, o.placed, o.max_runs);
     const size_t roll_at = b->path.find("+roll");  // (the path names the route where any image took it; other windows may change that)
     if (roll_at != std::string::npos) b->path.erase(roll_at, 5);
-    if (o.route.runs) b->path.insert(std::min(b->path.find("+warp"), b->path.size()), "+roll");  // (the last word of the u8 batch's path: in front of a warp's)
+    // (the last word of the u8 batch's path: in front of the colour's and the warp's)
+    if (o.route.runs) b->path.insert(std::min(std::min(b->path.find("+colour"), b->path.find("+warp")), b->path.size()), "+roll");
     B_HIP(batch_wait_enqueued(b));  // (a decode still queued reads the tables)
     if (o.tab.size() > o.tab_cap) {
         B_HIP(hipDeviceSynchronize());
@@ -221,6 +231,24 @@ static int upload_warp_jobs(jpgpu_batch *b, hipStream_t stream) {
     return JPGPU_OK;
 }
 
+// The ColourJobs of a coloured batch: every image's program and where the u8 resample left its pixels.  From a pinned mirror on the
+// decode's stream, as the WarpJobs: a decode queued earlier keeps the programs it was enqueued with.
+static int upload_colour_jobs(jpgpu_batch *b, hipStream_t stream) {
+    OutputStage &o = b->o;
+    const uint32_t n = (uint32_t)b->descs.size();
+    if (!o.h_cl_jobs) {
+        B_HIP(hipHostMalloc((void **)&o.h_cl_jobs, (size_t)n * sizeof(ColourJob), hipHostMallocDefault));
+        B_HIP(hipEventCreateWithFlags(&o.cl_sent, hipEventDisableTiming));
+    } else {
+        B_HIP(hipEventSynchronize(o.cl_sent));  // (the copy before this one has read the mirror)
+    }
+    for (uint32_t i = 0; i < n; i++) colour_job(o.h_cl_jobs[i], o.d_wsrc + o.wsrc_off[i], o.spec.w, o.spec.h, &o.programs[i]);
+    B_HIP(hipMemcpyAsync(o.d_cl_jobs, o.h_cl_jobs, (size_t)n * sizeof(ColourJob), hipMemcpyHostToDevice, stream));
+    B_HIP(hipEventRecord(o.cl_sent, stream));
+    o.cl_dirty = false;
+    return JPGPU_OK;
+}
+
 // On a refresh of the job tables (batch_refresh_jobs).  `all` false — nothing else is rebound: the records whose flips or matrices
 // changed, alone.  `all`: every record, with where the images lie in the arenas now; the blocking copies follow the caller's wait.
 int output_bind(jpgpu_batch *b, hipStream_t stream, bool all) {
@@ -230,6 +258,7 @@ int output_bind(jpgpu_batch *b, hipStream_t stream, bool all) {
     if (!all) {
         if (o.tn_dirty) rc = upload_tensor_jobs(b, stream);
         if (rc == JPGPU_OK && o.wp_dirty) rc = upload_warp_jobs(b, stream);
+        if (rc == JPGPU_OK && o.cl_dirty) rc = upload_colour_jobs(b, stream);
         return rc;
     }
     if (o.route.resample == Resample::None) return JPGPU_OK;
@@ -243,6 +272,7 @@ int output_bind(jpgpu_batch *b, hipStream_t stream, bool all) {
         B_HIP(hipMemcpy(o.d_or_jobs, o.or_jobs.data(), o.or_jobs.size() * sizeof(OrientJob), hipMemcpyHostToDevice));
     }
     if (o.route.warp) rc = upload_warp_jobs(b, stream);  // (the u8 resample of the same arguments writes the warp's source; the warp writes the output)
+    if (rc == JPGPU_OK && o.route.colour) rc = upload_colour_jobs(b, stream);  // (in place on the warp's source, between the two)
     if (rc) return rc;
     if (o.route.tensor_jobs()) return upload_tensor_jobs(b, stream);
     if (o.route.resample == Resample::Placed) {
@@ -260,7 +290,7 @@ int output_bind(jpgpu_batch *b, hipStream_t stream, bool all) {
 }
 
 // On a decode, behind the pixel kernels on `s`: the orientation launch, the route's resample launch, the launch of runs beside it, the
-// warp behind them.
+// colour launch and the warp behind them.
 int output_launch(jpgpu_batch *b, hipStream_t s) {
     const OutputStage &o = b->o;
     const uint32_t n = (uint32_t)b->descs.size(), es = o.spec.elem_bytes();
@@ -279,6 +309,10 @@ int output_launch(jpgpu_batch *b, hipStream_t s) {
         if (o.route.resample == Resample::Tensor)
             B_HIP(launch_resample_tensor_run(static_cast<const TensorJob *>(o.d_jobs) + n, o.d_tab, o.d_tn_table, o.d_bpr, es, n, o.max_runs, o.lds_bytes, s));
         else B_HIP(launch_resample_run(static_cast<const ResampleJob *>(o.d_jobs) + n, o.d_tab, o.d_bpr, n, o.max_runs, o.lds_bytes, s));
+    }
+    if (o.route.colour) {  // (the programs: behind the resample on the same stream, in place on what the warp launch reads)
+        if (o.cl_sent) B_HIP(hipStreamWaitEvent(s, o.cl_sent, 0));  // (the jobs may have gone up on another stream than this one)
+        B_HIP(launch_colour(o.d_cl_jobs, o.d_cl_scale, n, s));
     }
     if (o.route.warp) {  // (the warp: behind the resample on the same stream, from the second intermediate arena into the output arena)
         const uint32_t tiles = (o.spec.w * o.spec.h + WP_NT - 1u) / WP_NT;
@@ -301,13 +335,46 @@ int jpgpu_batch_set_flips(jpgpu_batch *b, const uint8_t *flips) {
 int jpgpu_batch_set_warps(jpgpu_batch *b, const jpgpu_warp *warps) {
     if (!b) return JPGPU_ERR_FORMAT;
     OutputStage &o = b->o;
-    if (!o.route.warp) return set_err(b->err, JPGPU_ERR_UNSUPPORTED, "jpgpu_batch_set_warps: the batch has no warp (jpgpu_batch_create_warped)");
+    if (!o.spec.warp) return set_err(b->err, JPGPU_ERR_UNSUPPORTED, "jpgpu_batch_set_warps: the batch has no warp (jpgpu_batch_create_warped)");
     for (size_t i = 0; warps && i < o.m.size(); i++)  // (one refused matrix refuses the call: nothing is changed)
         if (!warp_check(warps[i].m, o.spec.w, o.spec.h))
             return set_err(b->err, JPGPU_ERR_FORMAT, "jpgpu_batch_set_warps: image %zu: matrix (%g, %g, %g, %g, %g, %g) refused for %ux%u (jpgpu_warp_check)", i,
                            warps[i].m[0], warps[i].m[1], warps[i].m[2], warps[i].m[3], warps[i].m[4], warps[i].m[5], o.spec.w, o.spec.h);
     for (size_t i = 0; i < o.m.size(); i++) o.m[i] = warps ? warps[i] : kIdentity;
     o.wp_dirty = true;
+    return JPGPU_OK;
+}
+int jpgpu_batch_set_colour_programs(jpgpu_batch *b, const jpgpu_colour_program *programs) {
+    if (!b) return JPGPU_ERR_FORMAT;
+    OutputStage &o = b->o;
+    if (!o.route.colour) return set_err(b->err, JPGPU_ERR_UNSUPPORTED, "jpgpu_batch_set_colour_programs: the batch has no colour options (jpgpu_batch_create_coloured)");
+    std::string why;
+    for (size_t i = 0; programs && i < o.programs.size(); i++) {  // (one refused program refuses the call: nothing is changed)
+        const int rc = colour_program_rule(o.spec, b->descs[i].ncomp, as_program(programs[i]), why);
+        if (rc) return set_err(b->err, rc, "jpgpu_batch_set_colour_programs: image %zu: %s", i, why.c_str());
+    }
+    for (size_t i = 0; i < o.programs.size(); i++) o.programs[i] = programs ? as_program(programs[i]) : ColourProgram{};
+    o.cl_dirty = true;
+    return JPGPU_OK;
+}
+int jpgpu_colour_check(const jpgpu_colour_program *program) { return (program && colour_program_check(as_program(*program))) ? JPGPU_OK : JPGPU_ERR_FORMAT; }
+int jpgpu_colour_point_lut(uint32_t op, float value, uint32_t mean, uint8_t *lut) {
+    if (!lut || mean > 255u || op == CL_COLOR || op == CL_AUTOCONTRAST || op == CL_EQUALIZE || !colour_op_check(op, value)) return JPGPU_ERR_FORMAT;
+    for (uint32_t v = 0; v < 256u; v++) lut[v] = (uint8_t)cl_point_value(op, value, mean, v);
+    return JPGPU_OK;
+}
+int jpgpu_colour_autocontrast_lut(const uint32_t *h, uint8_t *lut) {
+    if (!h || !lut) return JPGPU_ERR_FORMAT;
+    double scale[256];
+    colour_scale_table(scale);
+    uint32_t lo, hi;
+    cl_hist_range(h, lo, hi);
+    for (uint32_t v = 0; v < 256u; v++) lut[v] = (uint8_t)cl_autocontrast_value(lo, hi, hi > lo ? scale[hi - lo] : 0.0, v);
+    return JPGPU_OK;
+}
+int jpgpu_colour_equalize_lut(const uint32_t *h, uint8_t *lut) {
+    if (!h || !lut) return JPGPU_ERR_FORMAT;
+    for (uint32_t v = 0; v < 256u; v++) lut[v] = (uint8_t)cl_equalize_value(h, v);
     return JPGPU_OK;
 }
 int jpgpu_oriented_window(uint32_t orientation, uint32_t w, uint32_t h, const jpgpu_window *oriented, uint32_t *oriented_w, uint32_t *oriented_h,

@@ -5,6 +5,7 @@
 #include <string.h>
 
 #include "batch_layout.hpp"
+#include "colour_band.hpp"
 #include "orient_band.hpp"
 #include "placed_band.hpp"
 #include "resample_band.hpp"
@@ -24,6 +25,7 @@ struct OutputSpec {
     bool warp = false;                  // warp options ...
     jpgpu_warp_options wp{};            // ... and which
     bool orient = false;                // some image has an EXIF orientation other than 1 (jpgpu_batch_create_oriented)
+    bool colour = false;                // colour options (jpgpu_batch_create_coloured): a program of colour operations per image
     bool sized() const { return w != 0 || h != 0; }
     uint32_t elem_bytes() const { return tensor ? tensor_elem_bytes(tn.dtype) : 1u; }
     uint32_t channels(uint32_t ncomp) const { return rgb ? 3u : ncomp; }
@@ -32,7 +34,7 @@ inline bool operator==(const OutputSpec &a, const OutputSpec &b) {
     return a.w == b.w && a.h == b.h && a.filter == b.filter && a.rgb == b.rgb && a.tensor == b.tensor && a.tn.dtype == b.tn.dtype &&
            a.tn.reserved == b.tn.reserved && memcmp(a.tn.mean, b.tn.mean, sizeof a.tn.mean) == 0 && memcmp(a.tn.std, b.tn.std, sizeof a.tn.std) == 0 &&
            memcmp(a.fill, b.fill, 4) == 0 && a.warp == b.warp && a.wp.filter == b.wp.filter && memcmp(a.wp.fill, b.wp.fill, 4) == 0 &&
-           a.wp.reserved == b.wp.reserved && a.orient == b.orient;
+           a.wp.reserved == b.wp.reserved && a.orient == b.orient && a.colour == b.colour;
 }
 inline uint32_t pack_fill(const uint8_t f[4]) { return (uint32_t)f[0] | ((uint32_t)f[1] << 8) | ((uint32_t)f[2] << 16) | ((uint32_t)f[3] << 24); }
 
@@ -47,6 +49,7 @@ inline int output_rule(const OutputSpec &s, std::string &why) {
     if (s.filter && !s.sized()) return why = std::string("a resample filter (") + resample_filter_name(s.filter) + ") needs an output size", JPGPU_ERR_UNSUPPORTED;
     if (s.rgb && !s.sized()) return why = "RGB output (JPGPU_BATCH_RGB_OUTPUT) needs an output size", JPGPU_ERR_UNSUPPORTED;
     if (s.orient && !s.sized()) return why = "EXIF orientations need an output size", JPGPU_ERR_UNSUPPORTED;
+    if (s.colour && !s.sized()) return why = "colour operations need an output size", JPGPU_ERR_UNSUPPORTED;
     if (s.warp && !s.sized()) return why = "a warp needs an output size", JPGPU_ERR_FORMAT;
     if (s.warp && (s.wp.filter > WP_BILINEAR || s.wp.reserved != 0))
         return no(JPGPU_ERR_FORMAT, "warp options: filter %u, reserved %u (JPGPU_WARP_NEAREST or JPGPU_WARP_BILINEAR, reserved 0)", s.wp.filter, s.wp.reserved);
@@ -119,19 +122,38 @@ inline size_t output_arena(const OutputSpec &s, const std::vector<jpgpu_image_de
     return arena_layout(lens, off, len);
 }
 
+// The C ABI's program as the kernels' record (the same layout, field by field)
+inline ColourProgram as_program(const jpgpu_colour_program &p) {
+    ColourProgram q{};
+    q.n = p.n;
+    for (uint32_t k = 0; k < CL_MAX_OPS && k < p.n; k++) q.ops[k] = ColourOp{p.ops[k].op, p.ops[k].value};
+    return q;
+}
+// A colour program against the image it is meant for: a refused program (colour_program_check) is JPGPU_ERR_FORMAT, a non-empty one on
+// an image whose output has another channel count than three JPGPU_ERR_UNSUPPORTED; the reason in `why`.
+inline int colour_program_rule(const OutputSpec &s, uint32_t ncomp, const ColourProgram &p, std::string &why) {
+    if (!colour_program_check(p))
+        return why = "colour program refused (at most 4 operations; factors 0..256; SOLARIZE 0..256 and POSTERIZE 1..8 in integers: jpgpu_colour_check)", JPGPU_ERR_FORMAT;
+    if (p.n != 0 && s.channels(ncomp) != 3u)
+        return why = "colour operations need three output channels (this image has " + std::to_string(s.channels(ncomp)) + "; RGB output gives three)", JPGPU_ERR_UNSUPPORTED;
+    return JPGPU_OK;
+}
+
 // The route: whether the orientation launch runs in front, which resample launch runs, whether the launch of runs of bands goes beside
-// it, whether a warp follows.  Allocation, job upload and launch switch on it.
+// it, whether the colour launch follows, whether a warp launch finishes.  Allocation, job upload and launch switch on it.  A coloured
+// batch always finishes through the warp launch — with identity matrices when it has no warp options (rule N-sep copies exactly and
+// applies the flip and the tensor table).
 enum class Resample : uint8_t { None, Band, Tensor, Placed, PlacedTensor };
 struct OutputRoute {
     Resample resample = Resample::None;
-    bool orient = false, runs = false, warp = false;
+    bool orient = false, runs = false, colour = false, warp = false;
     bool tensor_jobs() const { return resample == Resample::Tensor || resample == Resample::PlacedTensor; }
 };
 inline OutputRoute output_route(const OutputSpec &s, bool placed, uint32_t max_runs) {
     OutputRoute r;
     if (!s.sized()) return r;
-    r.warp = s.warp, r.orient = s.orient;
-    const bool tensor = s.tensor && !s.warp;  // (a warped batch resamples to u8, whatever it writes in the end)
+    r.colour = s.colour, r.warp = s.warp || s.colour, r.orient = s.orient;
+    const bool tensor = s.tensor && !s.warp && !s.colour;  // (a warped or coloured batch resamples to u8, whatever it writes in the end)
     r.resample = placed ? (tensor ? Resample::PlacedTensor : Resample::Placed) : (tensor ? Resample::Tensor : Resample::Band);
     r.runs = max_runs != 0 && !placed;
     return r;

@@ -260,6 +260,7 @@ struct SubBatch {
     std::vector<uint8_t> flips;       // a tensor batch: the flip of every image as the batch holds it (jpgpu_batch_set_flips)
     std::vector<jpgpu_placement> pls; // a fit: the placement of every image as the batch holds it
     std::vector<jpgpu_warp> warps;    // a warp: the matrix of every image as the batch holds it (jpgpu_batch_set_warps)
+    std::vector<jpgpu_colour_program> programs;  // colour: the program of every image as the batch holds it (jpgpu_batch_set_colour_programs)
     std::vector<uint8_t> orients;     // the EXIF orientation of every image as the batch was created with it; empty: all ones
     uint32_t remaining = 0;  // images not yet uploaded / failed (uploader thread only)
     hipEvent_t ready[kCopyStreams] = {nullptr, nullptr, nullptr, nullptr};
@@ -279,6 +280,7 @@ struct SubBatch {
         flips.clear();
         pls.clear();
         warps.clear();
+        programs.clear();
         orients.clear();
     }
 };
@@ -357,8 +359,8 @@ static const jpgpu_pipeline *child_of(const jpgpu_pipeline *p, uint32_t &image) 
     image /= n;
     return c;
 }
-static int multi_decode(jpgpu_pipeline *p, const uint8_t *const *data, const size_t *len, const jpgpu_window *windows, const uint8_t *flips, const jpgpu_warp *warps, uint32_t n,
-                        uint32_t flags);
+static int multi_decode(jpgpu_pipeline *p, const uint8_t *const *data, const size_t *len, const jpgpu_window *windows, const uint8_t *flips, const jpgpu_warp *warps,
+                        const jpgpu_colour_program *programs, uint32_t n, uint32_t flags);
 // Up to how many scans does a call walk its progressive frames a WAVE per scan (pipelined, huff_prog_job.hpp)?  Always: the launch
 // order keeps a frame's waves on one XCD, producers in front (csrc/batch_entropy.cpp), so an oversubscribed launch cannot starve a producer
 // (round 5's lanes had to fit the device at once).  Beyond the limit: a wave per TRACK, its scans one after the other —
@@ -633,6 +635,10 @@ int jpgpu_pipeline_decode_augmented(jpgpu_pipeline *p, const uint8_t *const *dat
                                     uint32_t n, uint32_t flags) {
     return jpgpu_pipeline_decode_warped(p, data, len, windows, flips, nullptr, n, flags);
 }
+int jpgpu_pipeline_decode_warped(jpgpu_pipeline *p, const uint8_t *const *data, const size_t *len, const jpgpu_window *windows, const uint8_t *flips,
+                                 const jpgpu_warp *warps, uint32_t n, uint32_t flags) {
+    return jpgpu_pipeline_decode_coloured(p, data, len, windows, flips, warps, nullptr, n, flags);
+}
 }  // extern "C"
 
 // What the steps of one decode call share: the call's arguments and what an earlier step leaves for the later ones.
@@ -640,9 +646,10 @@ struct Call {
     jpgpu_pipeline *p;
     const uint8_t *const *data;
     const size_t *len;
-    const jpgpu_window *windows;  // the arguments of jpgpu_pipeline_decode_warped (NULL: none)
+    const jpgpu_window *windows;  // the arguments of jpgpu_pipeline_decode_coloured (NULL: none)
     const uint8_t *flips;
     const jpgpu_warp *warps;
+    const jpgpu_colour_program *programs;
     uint32_t n, flags;
     bool download, compact, device_entropy, device_progressive;
     std::vector<jpgpu_image_desc> cand;  // per image: its descriptor, once its header is read
@@ -739,6 +746,11 @@ static void read_header(Call &c, uint32_t i) {
             snprintf(msg, sizeof msg, "warp: matrix (%g, %g, %g, %g, %g, %g) refused for %ux%u (jpgpu_warp_check)", m[0], m[1], m[2], m[3], m[4], m[5], p->out.w, p->out.h);
             throw DecodeError{JPGPU_ERR_FORMAT, msg};
         }
+        // (a program the colour stage refuses, or one for an image without three output channels, fails the image alone)
+        if (p->out.colour && c.programs) {
+            v = jpgpu::colour_program_rule(p->out, d.ncomp, jpgpu::as_program(c.programs[i]), why);
+            if (v != JPGPU_OK) throw DecodeError{v, "colour: " + why};
+        }
         // Eligible for the device?  A progressive frame: its scans as tracks (huff_prog_wave.hpp), if the stream is plainly eligible — how
         // many of a call's eligible frames really go there is decided once all headers are read; any other: the device entropy decoder.
         const bool prog = p->infos[i].coding_process == JPGPU_CODING_DCT_PROGRESSIVE;
@@ -827,6 +839,7 @@ static int prepare_sub_batch(Call &c, uint32_t j) {
     std::vector<uint8_t> fl;         // a tensor output: every image's flip
     std::vector<jpgpu_placement> pls;  // a fit: every image's placement
     std::vector<jpgpu_warp> wm;        // a warp: every image's matrix
+    std::vector<jpgpu_colour_program> cps;  // colour: every image's program, normalised (nothing behind its n operations)
     std::vector<uint8_t> ors;          // EXIF orientations: every image's (left empty when all are 1: the batch without the argument)
     bool sub_windowed = false, sub_oriented = false;
     for (uint32_t k = first; p->exif_orient && k < last; k++) sub_oriented = sub_oriented || p->orients[ok[k]] != 1;
@@ -840,6 +853,11 @@ static int prepare_sub_batch(Call &c, uint32_t j) {
         if (p->fit_on()) pls.push_back(p->places[ok[k]]);
         if (p->out.warp) wm.push_back(c.warps ? c.warps[ok[k]] : jpgpu_warp{{1.0, 0.0, 0.0, 0.0, 1.0, 0.0}});
         if (sub_oriented) ors.push_back(p->orients[ok[k]]);
+        if (p->out.colour) {
+            jpgpu_colour_program cp{};
+            for (uint32_t q = 0; c.programs && q < c.programs[ok[k]].n && q < 4u; q++) cp.ops[cp.n++] = c.programs[ok[k]].ops[q];
+            cps.push_back(cp);
+        }
     }
     sb.remaining = last - first;
     // Sub-batches of device-entropy images need no pinned staging for coefficients (their entropy-coded bytes are staged by
@@ -891,6 +909,7 @@ static int prepare_sub_batch(Call &c, uint32_t j) {
         sb.made_with = p->out, sb.fit = p->fit, sb.pls = pls, sb.orients = ors;
         sb.flips.assign(descs.size(), 0);
         sb.warps.assign(p->out.warp ? descs.size() : 0, jpgpu_warp{{1.0, 0.0, 0.0, 0.0, 1.0, 0.0}});
+        sb.programs.assign(p->out.colour ? descs.size() : 0, jpgpu_colour_program{});
         sb.compact = c.compact;
         sb.h_coef_bytes = jpgpu_batch_coef_arena_bytes(sb.batch);
         if (c.compact) {  // worst-case compact size per component (12 B/block more than dense), 256-B aligned
@@ -916,6 +935,12 @@ static int prepare_sub_batch(Call &c, uint32_t j) {
         rc = jpgpu_batch_set_warps(sb.batch, wm.data());
         if (rc) return jpgpu::set_err(p->err, rc, "%s", jpgpu_batch_last_error(sb.batch));
         sb.warps = wm;
+    }
+    // (other programs, kept or new: set in place like the matrices)
+    if (p->out.colour && memcmp(cps.data(), sb.programs.data(), cps.size() * sizeof(jpgpu_colour_program)) != 0) {
+        rc = jpgpu_batch_set_colour_programs(sb.batch, cps.data());
+        if (rc) return jpgpu::set_err(p->err, rc, "%s", jpgpu_batch_last_error(sb.batch));
+        sb.programs = cps;
     }
     if (c.download && (!sb.h_out || sb.h_out_bytes < jpgpu_batch_out_arena_bytes(sb.batch))) {
         if (sb.h_out) (void)hipHostFree(sb.h_out);
@@ -1330,8 +1355,8 @@ static void finish_timings(Call &c) {
 
 extern "C" {
 
-int jpgpu_pipeline_decode_warped(jpgpu_pipeline *p, const uint8_t *const *data, const size_t *len, const jpgpu_window *windows, const uint8_t *flips,
-                                 const jpgpu_warp *warps, uint32_t n, uint32_t flags) {
+int jpgpu_pipeline_decode_coloured(jpgpu_pipeline *p, const uint8_t *const *data, const size_t *len, const jpgpu_window *windows, const uint8_t *flips,
+                                   const jpgpu_warp *warps, const jpgpu_colour_program *programs, uint32_t n, uint32_t flags) {
     jpgpu::TraceRange roctx_range("jpgpu_pipeline_decode");
     // (unknown bits are refused, not ignored: 8u was round 2-3's JPGPU_PIPELINE_PROGRESSIVE_DELTAS, removed in round 4 — a caller built
     // against that header would otherwise silently get another transport: ADVICE r4)
@@ -1345,14 +1370,16 @@ int jpgpu_pipeline_decode_warped(jpgpu_pipeline *p, const uint8_t *const *data, 
     if (p && p->fit_on() && !p->out.w) return jpgpu::set_err(p->err, JPGPU_ERR_FORMAT, "jpgpu_pipeline_decode: a fit needs an output size (jpgpu_pipeline_set_output_size)");
     if (p && flips && !p->out.tensor) return jpgpu::set_err(p->err, JPGPU_ERR_FORMAT, "jpgpu_pipeline_decode_augmented: flips need a tensor output (jpgpu_pipeline_set_tensor_output)");
     if (p && warps && !p->out.warp) return jpgpu::set_err(p->err, JPGPU_ERR_FORMAT, "jpgpu_pipeline_decode_warped: warps need warp options (jpgpu_pipeline_set_warp)");
+    if (p && programs && !p->out.colour)
+        return jpgpu::set_err(p->err, JPGPU_ERR_FORMAT, "jpgpu_pipeline_decode_coloured: programs need colour options (jpgpu_pipeline_set_colour)");
     if (p && p->exif_orient && !p->out.w)
         return jpgpu::set_err(p->err, JPGPU_ERR_FORMAT, "jpgpu_pipeline_decode: EXIF orientation needs an output size (jpgpu_pipeline_set_output_size)");
-    if (p && !p->children.empty()) return (n && (!data || !len)) ? JPGPU_ERR_FORMAT : multi_decode(p, data, len, windows, flips, warps, n, flags);
+    if (p && !p->children.empty()) return (n && (!data || !len)) ? JPGPU_ERR_FORMAT : multi_decode(p, data, len, windows, flips, warps, programs, n, flags);
     if (!p || !p->pool || (n && (!data || !len))) return JPGPU_ERR_FORMAT;
     if ((flags & JPGPU_PIPELINE_GATHER) && !p->gather_on) flags &= ~(uint32_t)JPGPU_PIPELINE_GATHER;  // (one device: the pixels are where a gather would put them)
     int rc = jpgpu::use_device(p->device, p->err);
     if (rc) return rc;
-    Call c{p, data, len, windows, flips, warps, n, flags};
+    Call c{p, data, len, windows, flips, warps, programs, n, flags};
     c.t0 = now_ms(), c.cpu0 = process_cpu_ms();
     c.download = (flags & JPGPU_PIPELINE_DOWNLOAD) != 0, c.compact = (flags & JPGPU_PIPELINE_DENSE) == 0, c.device_entropy = (flags & JPGPU_PIPELINE_DEVICE_ENTROPY) != 0;
     c.device_progressive = c.device_entropy && (flags & JPGPU_PIPELINE_PROGRESSIVE_ON_HOST) == 0 && !getenv("JPGPU_PIPE_PROGRESSIVE_ON_HOST");
@@ -1544,6 +1571,13 @@ int jpgpu_pipeline_set_warp(jpgpu_pipeline *p, const jpgpu_warp_options *warp) {
     for (jpgpu_pipeline *c : p->children) jpgpu_pipeline_set_warp(c, warp);
     p->out.warp = warp != nullptr;
     p->out.wp = warp ? *warp : jpgpu_warp_options{};
+    return JPGPU_OK;
+}
+int jpgpu_pipeline_set_colour(jpgpu_pipeline *p, const jpgpu_colour_options *colour) {
+    if (!p) return JPGPU_ERR_FORMAT;
+    if (colour && colour->reserved != 0) return jpgpu::set_err(p->err, JPGPU_ERR_FORMAT, "colour options: reserved %u (must be 0)", colour->reserved);
+    for (jpgpu_pipeline *c : p->children) jpgpu_pipeline_set_colour(c, colour);
+    p->out.colour = colour != nullptr;
     return JPGPU_OK;
 }
 int jpgpu_pipeline_image_placement(const jpgpu_pipeline *p, uint32_t i, jpgpu_placement *out) {
@@ -1812,8 +1846,8 @@ int jpgpu_pipeline_last_timings(const jpgpu_pipeline *p, jpgpu_pipeline_timings 
 // copy of one sub-batch runs while the next ones decode; nothing to reduce — SURVEY 8e); jpgpu_pipeline_pixels_device then points
 // into the copies.  gather_ms = what the call still waited for the copies after the last child had decoded (the exposed part),
 // gather_copy_ms = the longest child's summed copy time (events around each copy).
-static int multi_decode(jpgpu_pipeline *p, const uint8_t *const *data, const size_t *len, const jpgpu_window *windows, const uint8_t *flips, const jpgpu_warp *warps, uint32_t n,
-                        uint32_t flags) {
+static int multi_decode(jpgpu_pipeline *p, const uint8_t *const *data, const size_t *len, const jpgpu_window *windows, const uint8_t *flips, const jpgpu_warp *warps,
+                        const jpgpu_colour_program *programs, uint32_t n, uint32_t flags) {
     const double t0 = now_ms(), cpu0 = process_cpu_ms();
     const uint32_t nc = (uint32_t)p->children.size();
     const bool gather = (flags & JPGPU_PIPELINE_GATHER) != 0;
@@ -1828,12 +1862,14 @@ static int multi_decode(jpgpu_pipeline *p, const uint8_t *const *data, const siz
     std::vector<std::vector<jpgpu_window>> cw(nc);
     std::vector<std::vector<uint8_t>> cf(nc);
     std::vector<std::vector<jpgpu_warp>> cm(nc);
+    std::vector<std::vector<jpgpu_colour_program>> cp(nc);
     for (uint32_t i = 0; i < n; i++) {
         cd[i % nc].push_back(data[i]);
         cl[i % nc].push_back(len[i]);
         if (windows) cw[i % nc].push_back(windows[i]);
         if (flips) cf[i % nc].push_back(flips[i]);
         if (warps) cm[i % nc].push_back(warps[i]);
+        if (programs) cp[i % nc].push_back(programs[i]);
     }
     std::vector<int> rcs(nc, JPGPU_OK);
     std::vector<std::thread> th;
@@ -1842,8 +1878,8 @@ static int multi_decode(jpgpu_pipeline *p, const uint8_t *const *data, const siz
         p->children[k]->gather_device = p->device;
         th.emplace_back([&, k] {
             pin_to(p->child_cpus[k]);  // (the call's uploader thread starts from here and inherits the mask)
-            rcs[k] = jpgpu_pipeline_decode_warped(p->children[k], cd[k].data(), cl[k].data(), windows ? cw[k].data() : nullptr, flips ? cf[k].data() : nullptr,
-                                                  warps ? cm[k].data() : nullptr, (uint32_t)cd[k].size(), child_flags);
+            rcs[k] = jpgpu_pipeline_decode_coloured(p->children[k], cd[k].data(), cl[k].data(), windows ? cw[k].data() : nullptr, flips ? cf[k].data() : nullptr,
+                                                    warps ? cm[k].data() : nullptr, programs ? cp[k].data() : nullptr, (uint32_t)cd[k].size(), child_flags);
         });
     }
     for (auto &t : th) t.join();

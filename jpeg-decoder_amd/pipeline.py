@@ -10,6 +10,7 @@ import numpy as np
 
 from . import _native as N
 from .batch import filter_id, flip_bytes, output_size_pair, warp_structs, window_structs
+from .colour import program_structs
 from .decoder import CODING_PROCESSES, PIXEL_FORMATS, ImageInfo
 from .error import check, error_for_status
 from .worker import color_transform_id
@@ -76,7 +77,7 @@ class Pipeline:
 
     def decode(self, streams, download=True, dense=False, device_entropy=True, scale=None, color_transform=None, max_decoding_buffer_size=None,
                gather=False, host_light=None, input_pinned=False, progressive_on_host=False, windows=None, output_size=None,
-               tensor=None, flips=None, rgb=False, fit=None, filter=None, warp=None, warps=None, exif_orientation=False):
+               tensor=None, flips=None, rgb=False, fit=None, filter=None, warp=None, warps=None, exif_orientation=False, colour=None, colours=None):
         """-> list with, per stream, a numpy uint8 array of the decoded pixels (``Decoder.decode()``'s Vec<u8>) or the
         ``Error`` instance that stream produced.  download=False leaves the pixels in HBM (see ``device_pointer``); dense=True sends all
         64 coefficients of every block over PCIe instead of the compact form (same pixels, A/B switch); device_entropy=True
@@ -126,7 +127,12 @@ class Pipeline:
         exif_orientation: True (jpgpu_pipeline_set_exif_orientation, set on every call; needs output_size, else FormatError and nothing
         is decoded): every stream is oriented by its EXIF orientation tag in front of the output size — ``ImageOps.exif_transpose`` —
         and `windows` and `fit` are meant on the oriented image.  ``orientation(i)`` gives the value applied (1 for a
-        file without the tag or with damaged EXIF), ``window(i)`` the window in oriented coordinates, ``info(i)`` keeps the file's size."""
+        file without the tag or with damaged EXIF), ``window(i)`` the window in oriented coordinates, ``info(i)`` keeps the file's size.
+        colour: True (jpgpu_pipeline_set_colour, set on every call; needs output_size, else FormatError and nothing is decoded): a
+        colour stage behind the resample, before the warp and the tensor table.  colours: None (empty programs) or a
+        list with a program — at most four ``(name, value)`` pairs, see ``Batch.set_colour`` — or None per stream (needs `colour`, else
+        FormatError and nothing is decoded); a program the library refuses, or a non-empty one for a stream without three output
+        channels, fails its stream alone.  Fresh programs for the same files keep the pipeline's sub-batches."""
         if isinstance(streams, PinnedFiles):
             bufs = None
             n = len(streams)
@@ -139,6 +145,7 @@ class Pipeline:
         size = (0, 0) if output_size is None else output_size_pair(output_size)
         flip_arr = flip_bytes(flips, n)
         warp_arr = warp_structs(warps, n)
+        colour_arr = program_structs(colours, n)
         filt = filter_id(filter)
         fmt = None if tensor is None else tensor.struct()
         self._shape = None if tensor is None else (tensor.numpy_dtype, size[1], size[0])
@@ -160,6 +167,9 @@ class Pipeline:
         warp_s = None if warp is None else warp.struct()
         st = L.jpgpu_pipeline_set_warp(self._h, None if warp_s is None else C.byref(warp_s))
         check(st, L.jpgpu_pipeline_last_error(self._h) if st else b"")
+        colour_s = N.ColourOptionsStruct(0) if colour else None
+        st = L.jpgpu_pipeline_set_colour(self._h, None if colour_s is None else C.byref(colour_s))
+        check(st, L.jpgpu_pipeline_last_error(self._h) if st else b"")
         if bufs is None:
             ptrs = (C.c_void_p * max(n, 1))(*[streams.base + o for o in streams.offsets])
             lens = (C.c_size_t * max(n, 1))(*streams.lengths)
@@ -170,7 +180,9 @@ class Pipeline:
         flags = ((N.PIPELINE_DOWNLOAD if download else 0) | (N.PIPELINE_DENSE if dense else 0) | (N.PIPELINE_DEVICE_ENTROPY if device_entropy else 0) |
                  (N.PIPELINE_GATHER if gather else 0) | (N.PIPELINE_INPUT_PINNED if input_pinned else 0) | (N.PIPELINE_PROGRESSIVE_ON_HOST if progressive_on_host else 0) |
                  (0 if host_light is None else (N.PIPELINE_HOST_LIGHT if host_light else N.PIPELINE_HOST_STAGED)))
-        if warp_arr is not None or warp is not None:
+        if colour_arr is not None or colour:
+            st = L.jpgpu_pipeline_decode_coloured(self._h, C.cast(ptrs, C.POINTER(C.c_void_p)), lens, wins, flip_arr, warp_arr, colour_arr, n, flags)
+        elif warp_arr is not None or warp is not None:
             st = L.jpgpu_pipeline_decode_warped(self._h, C.cast(ptrs, C.POINTER(C.c_void_p)), lens, wins, flip_arr, warp_arr, n, flags)
         elif flip_arr is not None:
             st = L.jpgpu_pipeline_decode_augmented(self._h, C.cast(ptrs, C.POINTER(C.c_void_p)), lens, wins, flip_arr, n, flags)
