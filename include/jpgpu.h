@@ -445,7 +445,14 @@ uint32_t jpgpu_exif_orientation(const uint8_t *exif, size_t len);
  * Only images whose output has three channels take a non-empty program (RGB / YCbCr sources, or any source under
  * JPGPU_BATCH_RGB_OUTPUT): another one is JPGPU_ERR_UNSUPPORTED.  A program is refused (jpgpu_colour_check: JPGPU_ERR_FORMAT) for
  * n > 4, an unknown operation, a factor that is not finite, negative or above 256, a SOLARIZE value that is no integer in 0..256, a
- * POSTERIZE value that is no integer in 1..8.
+ * POSTERIZE value that is no integer in 1..8, a HUE value that is no integer in 0..255.
+ * Operations from 16 on are not tables; both equal Pillow byte for byte:
+ *    16 HUE           shift n      (h, s, v) = rgb2hsv(px); h = (h + n) & 255; hsv2rgb        P.convert("HSV"), h + n, .convert("RGB"):
+ *                                  n an integer 0..255; n = 0 is the lossy round trip          torchvision's adjust_hue on a PIL image
+ *    17 SHARPNESS     factor f     blend(SMOOTH(P), p, f) per channel value                   ImageEnhance.Sharpness(P).enhance(f)
+ *   rgb2hsv / hsv2rgb: Pillow's (Convert.c), float32 and double arithmetic with every operation rounded once, IEEE divisions.
+ *   SMOOTH: the 3 x 3 filter (1 1 1, 1 5 1, 1 1 1) / 13 in float32 — 0.5f, then the three rows from the one below upwards, each
+ *     (left k + middle k') + right k — truncated; the outermost row and column of every side are copied (W < 3 or H < 3: P itself).
  * `colour` NULL IS jpgpu_batch_create_oriented: same kernels, launches, bytes and path.  Otherwise every image starts with the empty
  * program; the batch's resample launch is the u8 one of the same arguments and writes the arena a warp reads, one launch behind it
  * (a workgroup per image) runs the programs there in place, and the batch's warp launch — with identity matrices in a batch without
@@ -453,7 +460,9 @@ uint32_t jpgpu_exif_orientation(const uint8_t *exif, size_t len);
  * output size: JPGPU_ERR_UNSUPPORTED, as RGB output; reserved != 0: JPGPU_ERR_FORMAT. */
 enum {
     JPGPU_COLOUR_IDENTITY = 0, JPGPU_COLOUR_BRIGHTNESS = 1, JPGPU_COLOUR_CONTRAST = 2, JPGPU_COLOUR_COLOR = 3, JPGPU_COLOUR_SOLARIZE = 4,
-    JPGPU_COLOUR_POSTERIZE = 5, JPGPU_COLOUR_INVERT = 6, JPGPU_COLOUR_AUTOCONTRAST = 7, JPGPU_COLOUR_EQUALIZE = 8
+    JPGPU_COLOUR_POSTERIZE = 5, JPGPU_COLOUR_INVERT = 6, JPGPU_COLOUR_AUTOCONTRAST = 7, JPGPU_COLOUR_EQUALIZE = 8,
+    /* operations from 16 on are not tables (below); ids 9..15 and from 18 on are refused */
+    JPGPU_COLOUR_HUE = 16, JPGPU_COLOUR_SHARPNESS = 17
 };
 typedef struct jpgpu_colour_op {
     uint32_t op; /* JPGPU_COLOUR_* */
@@ -483,6 +492,11 @@ int jpgpu_colour_check(const jpgpu_colour_program *program);
 int jpgpu_colour_point_lut(uint32_t op, float value, uint32_t mean, uint8_t *lut);
 int jpgpu_colour_autocontrast_lut(const uint32_t *h, uint8_t *lut);
 int jpgpu_colour_equalize_lut(const uint32_t *h, uint8_t *lut);
+/* Programs on a caller's pixels: d_pixels holds n images of h x w x 3 bytes on the current device, one behind the other, and image i
+ * goes through programs[i] in place, by the launch a coloured batch makes (`hip_stream`: a hipStream_t; NULL = the null stream).  The
+ * call returns when the work is complete.  The programs are checked first: one refused program refuses the call, JPGPU_ERR_FORMAT,
+ * and nothing is written.  d_pixels must be 256-byte aligned, 3 w h a multiple of 4, w and h 1..2048: else JPGPU_ERR_UNSUPPORTED. */
+int jpgpu_colour_apply(uint8_t *d_pixels, uint32_t n, uint32_t w, uint32_t h, const jpgpu_colour_program *programs, void *hip_stream);
 void jpgpu_batch_destroy(jpgpu_batch *b);
 const char *jpgpu_batch_last_error(const jpgpu_batch *b);
 

@@ -199,6 +199,7 @@ _PROTOS = {
     "jpgpu_colour_point_lut": (C.c_int, [C.c_uint32, C.c_float, C.c_uint32, C.c_void_p]),
     "jpgpu_colour_autocontrast_lut": (C.c_int, [C.c_void_p, C.c_void_p]),
     "jpgpu_colour_equalize_lut": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "jpgpu_colour_apply": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(ColourProgram), C.c_void_p]),
     "jpgpu_oriented_window": (C.c_int, [C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(Window), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(Window)]),
     "jpgpu_exif_orientation": (C.c_uint32, [C.c_void_p, C.c_size_t]),
     "jpgpu_warp_check": (C.c_int, [C.POINTER(Warp), C.c_uint32, C.c_uint32]),

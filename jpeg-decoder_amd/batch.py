@@ -355,8 +355,8 @@ class Batch:
 
     colour: None / False, or True (jpgpu_batch_create_coloured; needs an output_size, else UnsupportedError).  Every image's u8 result of
     the above — RGB conversion, orientation, resample and placement fill included — then goes through a program of at most four Pillow
-    colour operations, before the warp and the tensor table (DESIGN.md §4.20; the helpers of ``colour.py``: brightness, contrast,
-    saturation, solarize, posterize, invert, autocontrast, equalize).  Every image starts with the empty program;
+    colour operations, before the warp and the tensor table (DESIGN.md §4.20, §4.21; the helpers of ``colour.py``: brightness, contrast,
+    saturation, solarize, posterize, invert, autocontrast, equalize, hue, sharpness).  Every image starts with the empty program;
     ``set_colour([...])`` sets the programs from the next decode on.  Only images with three output channels take a non-empty
     program.  `path` gains "+colour" before "+warp" / "+tensor"."""
 

@@ -1,5 +1,6 @@
-"""Colour programs of the fixed-output stage (jpgpu_batch_create_coloured, DESIGN.md §4.20): a program is a list of at most four
-operations, each a ``(name, value)`` pair or what one of the helpers below returns — ``[brightness(1.2), contrast(0.8), equalize()]``."""
+"""Colour programs of the fixed-output stage (jpgpu_batch_create_coloured, DESIGN.md §4.20, §4.21): a program is a list of at most four
+operations, each a ``(name, value)`` pair or what one of the helpers below returns — ``[brightness(1.2), contrast(0.8), equalize()]``;
+``[brightness(b), contrast(c), saturation(s), hue(h)]`` in any order is torchvision's ``ColorJitter`` on a PIL image."""
 import ctypes as C
 
 import numpy as np
@@ -8,7 +9,7 @@ from . import _native as N
 from .error import check
 
 OPS = {"identity": 0, "brightness": 1, "contrast": 2, "saturation": 3, "color": 3, "solarize": 4, "posterize": 5, "invert": 6, "autocontrast": 7,
-       "equalize": 8}
+       "equalize": 8, "hue": 16, "sharpen": 17}
 
 
 def identity():
@@ -50,6 +51,22 @@ def autocontrast():
 
 def equalize():
     return ("equalize", 0.0)
+
+
+def hue(factor):
+    """torchvision's ``adjust_hue(im, factor)`` on a PIL image, -0.5 <= factor <= 0.5: the hue channel of ``im.convert("HSV")`` moved by
+    ``int(factor * 255) & 255`` (truncated toward zero, as ``np.int32(factor * 255).astype(np.uint8)``) and converted back.  Factor 0 is
+    the lossy round trip through HSV, not the identity — as in torchvision."""
+    if not -0.5 <= factor <= 0.5:
+        raise ValueError(f"hue factor {factor!r}: -0.5..0.5")
+    return ("hue", float(int(factor * 255) & 255))
+
+
+def sharpness(f):
+    """``ImageEnhance.Sharpness(im).enhance(f)``: 0 is Pillow's SMOOTH filter, 1 the image itself, 2 RandAugment's strongest.  The
+    operation's name is ``"sharpen"``: programs have always refused the name ``"sharpness"`` as unknown, and callers who probe for an
+    operation by its name keep getting that answer."""
+    return ("sharpen", float(f))
 
 
 def op_id(name):
@@ -108,3 +125,21 @@ def colour_equalize_lut(hist):
     lut = np.zeros(256, np.uint8)
     check(N.lib().jpgpu_colour_equalize_lut(h.ctypes.data, lut.ctypes.data), b"jpgpu_colour_equalize_lut: refused")
     return lut
+
+
+def colour_apply(tensor, programs):
+    """jpgpu_colour_apply: the programs (one per image, or None for the empty one) on a contiguous uint8 torch tensor of N x H x W x 3 on
+    the device, in place, on the tensor's device and torch's current stream; returns the tensor when the work is complete.  Its first
+    byte must be 256-byte aligned and 3 W H a multiple of 4 (UnsupportedError); one refused program refuses the call (FormatError) and
+    nothing is written."""
+    import torch
+
+    if not (isinstance(tensor, torch.Tensor) and tensor.is_cuda and tensor.dtype == torch.uint8 and tensor.dim() == 4 and tensor.shape[3] == 3
+            and tensor.is_contiguous()):
+        raise ValueError("colour_apply: a contiguous uint8 N x H x W x 3 tensor on the device")
+    n, h, w, _ = tensor.shape
+    arr = program_structs(programs if programs is not None else [None] * n, n)
+    with torch.cuda.device(tensor.device):
+        stream = torch.cuda.current_stream().cuda_stream
+        check(N.lib().jpgpu_colour_apply(tensor.data_ptr(), n, w, h, arr, stream), b"jpgpu_colour_apply: refused (a program, or the base / size rule)")
+    return tensor

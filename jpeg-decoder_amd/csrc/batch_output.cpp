@@ -4,8 +4,16 @@
 #include <map>
 
 #include "batch_internal.hpp"
+#include "colour_pixel_band.hpp"
 
 static const jpgpu_warp kIdentity{{1.0, 0.0, 0.0, 0.0, 1.0, 0.0}};
+// JPGPU_CL_STRIP_ROWS, read per call: the rows of a SHARPNESS strip (clamped by cl_strip_rows to what LDS holds); unset or 0: as many
+// as LDS holds.  The tests reach strip seams on small images with it.
+static uint32_t colour_strip_rows_knob() {
+    const char *knob = getenv("JPGPU_CL_STRIP_ROWS");
+    const int v = knob ? atoi(knob) : 0;
+    return v > 0 ? (uint32_t)v : 0u;
+}
 static size_t warp_jobs_bytes(const jpgpu_batch *b) { return b->descs.size() * (sizeof(WarpJob) + ((size_t)b->o.spec.w + b->o.spec.h) * sizeof(int32_t)); }
 
 // At creation, once the intermediate arena is laid out as the output arena (out_off, out_len, out_bytes): that layout becomes the
@@ -312,7 +320,7 @@ int output_launch(jpgpu_batch *b, hipStream_t s) {
     }
     if (o.route.colour) {  // (the programs: behind the resample on the same stream, in place on what the warp launch reads)
         if (o.cl_sent) B_HIP(hipStreamWaitEvent(s, o.cl_sent, 0));  // (the jobs may have gone up on another stream than this one)
-        B_HIP(launch_colour(o.d_cl_jobs, o.d_cl_scale, n, s));
+        B_HIP(launch_colour(o.d_cl_jobs, o.d_cl_scale, n, colour_strip_rows_knob(), s));
     }
     if (o.route.warp) {  // (the warp: behind the resample on the same stream, from the second intermediate arena into the output arena)
         const uint32_t tiles = (o.spec.w * o.spec.h + WP_NT - 1u) / WP_NT;
@@ -359,7 +367,7 @@ int jpgpu_batch_set_colour_programs(jpgpu_batch *b, const jpgpu_colour_program *
 }
 int jpgpu_colour_check(const jpgpu_colour_program *program) { return (program && colour_program_check(as_program(*program))) ? JPGPU_OK : JPGPU_ERR_FORMAT; }
 int jpgpu_colour_point_lut(uint32_t op, float value, uint32_t mean, uint8_t *lut) {
-    if (!lut || mean > 255u || op == CL_COLOR || op == CL_AUTOCONTRAST || op == CL_EQUALIZE || !colour_op_check(op, value)) return JPGPU_ERR_FORMAT;
+    if (!lut || mean > 255u || op == CL_COLOR || op == CL_AUTOCONTRAST || op == CL_EQUALIZE || op >= CL_PIXEL_OPS || !colour_op_check(op, value)) return JPGPU_ERR_FORMAT;
     for (uint32_t v = 0; v < 256u; v++) lut[v] = (uint8_t)cl_point_value(op, value, mean, v);
     return JPGPU_OK;
 }
@@ -376,6 +384,33 @@ int jpgpu_colour_equalize_lut(const uint32_t *h, uint8_t *lut) {
     if (!h || !lut) return JPGPU_ERR_FORMAT;
     for (uint32_t v = 0; v < 256u; v++) lut[v] = (uint8_t)cl_equalize_value(h, v);
     return JPGPU_OK;
+}
+// A program per image on the caller's pixels: the jobs and the scale table go up, the colour kernel runs on `stream`, and the call
+// returns behind it.
+int jpgpu_colour_apply(uint8_t *d_pixels, uint32_t n, uint32_t w, uint32_t h, const jpgpu_colour_program *programs, void *hip_stream) {
+    hipStream_t stream = static_cast<hipStream_t>(hip_stream);
+    if (n == 0) return JPGPU_OK;
+    if (!d_pixels || !programs) return JPGPU_ERR_FORMAT;
+    for (uint32_t i = 0; i < n; i++)  // (one refused program refuses the call: nothing is written)
+        if (!colour_program_check(as_program(programs[i]))) return JPGPU_ERR_FORMAT;
+    const size_t image = (size_t)3u * w * h;
+    if (w == 0 || h == 0 || w > CL_MAX_SIDE || h > CL_MAX_SIDE || ((uintptr_t)d_pixels & 255u) != 0 || (image & 3u) != 0) return JPGPU_ERR_UNSUPPORTED;
+    std::vector<ColourJob> jobs(n);
+    for (uint32_t i = 0; i < n; i++) {
+        const ColourProgram p = as_program(programs[i]);
+        colour_job(jobs[i], d_pixels + (size_t)i * image, w, h, &p);
+    }
+    double scale[256];
+    colour_scale_table(scale);
+    const size_t jobs_bytes = (size_t)n * sizeof(ColourJob);
+    uint8_t *d_block = nullptr;  // (the scale table, then the jobs)
+    if (hipMalloc((void **)&d_block, sizeof scale + jobs_bytes) != hipSuccess) return JPGPU_ERR_IO;
+    hipError_t e = hipMemcpyAsync(d_block, scale, sizeof scale, hipMemcpyHostToDevice, stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(d_block + sizeof scale, jobs.data(), jobs_bytes, hipMemcpyHostToDevice, stream);
+    if (e == hipSuccess) e = launch_colour(reinterpret_cast<const ColourJob *>(d_block + sizeof scale), reinterpret_cast<const double *>(d_block), n, colour_strip_rows_knob(), stream);
+    const hipError_t done = hipStreamSynchronize(stream);  // (the host blocks above are read by now, whatever failed)
+    (void)hipFree(d_block);
+    return e == hipSuccess && done == hipSuccess ? JPGPU_OK : JPGPU_ERR_IO;
 }
 int jpgpu_oriented_window(uint32_t orientation, uint32_t w, uint32_t h, const jpgpu_window *oriented, uint32_t *oriented_w, uint32_t *oriented_h,
                           jpgpu_window *source) {

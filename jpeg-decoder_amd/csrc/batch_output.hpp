@@ -133,7 +133,7 @@ inline ColourProgram as_program(const jpgpu_colour_program &p) {
 // an image whose output has another channel count than three JPGPU_ERR_UNSUPPORTED; the reason in `why`.
 inline int colour_program_rule(const OutputSpec &s, uint32_t ncomp, const ColourProgram &p, std::string &why) {
     if (!colour_program_check(p))
-        return why = "colour program refused (at most 4 operations; factors 0..256; SOLARIZE 0..256 and POSTERIZE 1..8 in integers: jpgpu_colour_check)", JPGPU_ERR_FORMAT;
+        return why = "colour program refused (at most 4 operations; factors 0..256; SOLARIZE 0..256, POSTERIZE 1..8 and HUE 0..255 in integers: jpgpu_colour_check)", JPGPU_ERR_FORMAT;
     if (p.n != 0 && s.channels(ncomp) != 3u)
         return why = "colour operations need three output channels (this image has " + std::to_string(s.channels(ncomp)) + "; RGB output gives three)", JPGPU_ERR_UNSUPPORTED;
     return JPGPU_OK;

@@ -4,7 +4,8 @@
 //     C = op_{k-1}( ... op_1( op_0( R ) ) )
 // Every operation but COLOR is a table of 3 x 256 bytes looked up per channel value, some after a pass of statistics over the CURRENT
 // image (CONTRAST: the sum of L; AUTOCONTRAST, EQUALIZE: the histograms); COLOR blends every pixel with its own L.  The arithmetic is
-// Pillow's, stated here once for the device, the host functions and the CPU emulation:
+// Pillow's, stated here once for the device, the host functions and the CPU emulation (HUE and SHARPNESS, the operations from id 16 on
+// that are not tables, walk the same program by steps of their own: colour_pixel_band.hpp):
 //   blend(a, b, f)   IEEE float32, the product and the sum rounded once each (cl_mulf / cl_addf: no fused multiply-add):
 //                    t = (float)a + f * (float)(b - a); 0 <= f <= 1: (uint8)(int)t; else t <= 0: 0, t >= 255: 255, else (uint8)(int)t.
 //   L(px)            (R 19595 + G 38470 + B 7471 + 0x8000) >> 16                                        (convert("L"))
@@ -39,6 +40,8 @@ namespace jpgpu {
 // JPGPU_COLOUR_*
 constexpr uint32_t CL_IDENTITY = 0, CL_BRIGHTNESS = 1, CL_CONTRAST = 2, CL_COLOR = 3, CL_SOLARIZE = 4, CL_POSTERIZE = 5, CL_INVERT = 6, CL_AUTOCONTRAST = 7,
                    CL_EQUALIZE = 8, CL_OPS = 9;
+// Operations from 16 on are not tables (colour_pixel_band.hpp): ids 9..15 and from 18 on are refused
+constexpr uint32_t CL_PIXEL_OPS = 16, CL_HUE = 16, CL_SHARPNESS = 17, CL_PIXEL_OPS_END = 18;
 constexpr uint32_t CL_MAX_OPS = 4;        // operations of a program
 constexpr uint32_t CL_NT = 1024;          // lanes of a workgroup
 constexpr uint32_t CL_PHASES = 4;         // zero, accumulate, table, apply
@@ -66,8 +69,11 @@ struct ColourLds {
 };
 
 // The refusal rule of one operation: an unknown id; a factor that is not finite, negative or above 256; a SOLARIZE value that is no
-// integer in 0..256; a POSTERIZE value that is no integer in 1..8.  The other operations ignore their value.
+// integer in 0..256; a POSTERIZE value that is no integer in 1..8; a HUE shift that is no integer in 0..255; a SHARPNESS factor as the
+// other factors.  The other operations ignore their value.
 inline bool colour_op_check(uint32_t op, float value) {
+    if (op == CL_HUE) return value >= 0.0f && value <= 255.0f && value == floorf(value);
+    if (op == CL_SHARPNESS) return value >= 0.0f && value <= CL_MAX_FACTOR;
     if (op >= CL_OPS) return false;
     if (op == CL_BRIGHTNESS || op == CL_CONTRAST || op == CL_COLOR) return value >= 0.0f && value <= CL_MAX_FACTOR;  // (NaN compares false)
     if (op == CL_SOLARIZE) return value >= 0.0f && value <= 256.0f && value == floorf(value);
@@ -96,7 +102,8 @@ inline void colour_scale_table(double t[256]) {
 
 // IEEE float32 / double, rounded once per operation.  hipcc contracts a + f * d into a fused multiply-add by default, across statements:
 // the pragma takes the permission from the operation itself (warp_band.hpp: wp_mul), and the kernel's disassembly must show no v_fma /
-// v_fmac in these paths (profiles/colour/).  The host's versions store the result before it is used.
+// v_fmac in these paths (profiles/colour/; the divisions of HUE are the only fused operations of the kernel:
+// colour_pixel_kernel_resources.txt).  The host's versions store the result before it is used.
 JP_CL_BOTH static inline float cl_mulf(float a, float b) {
 #if defined(__HIP_DEVICE_COMPILE__)
 #pragma clang fp contract(off)
@@ -328,7 +335,8 @@ struct CBand {
 
 #if defined(__HIP__) && !defined(JPGPU_HOST_EMULATION)
 namespace jpgpu {
-// colour.hip: n_images jobs, a workgroup each, on `stream`; d_scale: colour_scale_table on the device
-hipError_t launch_colour(const ColourJob *d_jobs, const double *d_scale, uint32_t n_images, hipStream_t stream);
+// colour.hip: n_images jobs, a workgroup each, on `stream`; d_scale: colour_scale_table on the device; strip_rows: the rows of a
+// SHARPNESS strip when not 0 (colour_pixel_band.hpp: cl_strip_rows)
+hipError_t launch_colour(const ColourJob *d_jobs, const double *d_scale, uint32_t n_images, uint32_t strip_rows, hipStream_t stream);
 }  // namespace jpgpu
 #endif

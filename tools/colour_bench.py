@@ -1,4 +1,4 @@
-"""The colour stage (DESIGN.md §4.20) on the BASELINE workload (1920x1080 4:2:0 q85): what it adds to a loader's call.
+"""The colour stage (DESIGN.md §4.20, §4.21) on the BASELINE workload (1920x1080 4:2:0 q85): what it adds to a loader's call.
 
 Pixel stage (coefficients resident in HBM -> tensors in HBM, 256 resident images, a quarter window of each to 224 x 224 f32), all in one
 run, interleaved call by call, each figure the median over --reps calls of jpgpu_batch_time (--iters decodes between two events):
@@ -7,12 +7,15 @@ run, interleaved call by call, each figure the median over --reps calls of jpgpu
     bcs          — brightness + contrast + saturation on every image
     equalize     — equalize alone
     solarize     — solarize alone
+    hue          — hue alone (the HSV round trip per pixel, §4.21)
+    sharpen      — sharpen alone (strips through LDS, §4.21)
+    jitter       — ColorJitter's four: brightness + contrast + saturation + hue
 beside the window kernel alone (the same windows without an output size: the resample launch's own time is `off` minus it).
 
     python tools/colour_bench.py --out profiles/colour/colour_bench.json --commit <sha>
 
---e2e: from JPEG bytes to HBM through Pipeline.decode(windows=, output_size=, tensor=[, colour=, colours=]), 256 files, off and bcs, one
-pipeline per configuration, interleaved call by call, median of --reps warm calls.  --first off|on: which pipeline the process creates
+--e2e: from JPEG bytes to HBM through Pipeline.decode(windows=, output_size=, tensor=[, colour=, colours=]), 256 files, off and the program
+--program names (bcs), one pipeline per configuration, interleaved call by call, median of --reps warm calls.  --first off|on: which pipeline the process creates
 first (the pipeline a process creates first runs its calls faster than a later one whatever it decodes, DESIGN.md §4.11: run both orders,
 a process each, and take the mean).
 
@@ -30,7 +33,7 @@ for p in (ROOT, os.path.join(ROOT, "tests"), os.path.join(ROOT, "tools")):
     if p not in sys.path:
         sys.path.insert(0, p)
 
-import colour_ref as CR  # noqa: E402
+import colour_pixel_ref as CR  # noqa: E402  (apply: the table operations and the pixel ones)
 import jpeg_decoder_amd as J  # noqa: E402
 import resize_bench as RB  # noqa: E402
 import synth  # noqa: E402
@@ -39,9 +42,10 @@ import window_bench as WB  # noqa: E402
 
 W, H, N = WB.W, WB.H, WB.N
 SIZE = (224, 224)
-RB.SOURCES = RB.SOURCES + ("warp_band.hpp", "warp.hip", "colour_band.hpp", "colour.hip")
+RB.SOURCES = RB.SOURCES + ("warp_band.hpp", "warp.hip", "colour_band.hpp", "colour_pixel_band.hpp", "colour.hip")
 FMT = J.TensorFormat("float32", T.IMAGENET[0], T.IMAGENET[1])
-PROGRAMS = {"empty": None, "bcs": [("brightness", 1.2), ("contrast", 0.8), ("saturation", 1.3)], "equalize": [("equalize", 0)], "solarize": [("solarize", 128)]}
+PROGRAMS = {"empty": None, "bcs": [("brightness", 1.2), ("contrast", 0.8), ("saturation", 1.3)], "equalize": [("equalize", 0)], "solarize": [("solarize", 128)],
+            "hue": [("hue", 43)], "sharpen": [("sharpen", 1.9)], "jitter": [("brightness", 1.2), ("contrast", 0.8), ("saturation", 1.3), ("hue", 43)]}
 
 
 def quarter(k):
@@ -147,9 +151,9 @@ def e2e(args):
     wins = [quarter(k) for k in range(n)]
     doc = RB.header("tools/colour_bench.py --e2e", args)
     doc.update({"files": who, "workload": f"{W}x{H} 4:2:0 q85 files ({len(distinct)} distinct), a quarter window of each to 224x224 f32, through Pipeline.decode to HBM",
-                "program": PROGRAMS["bcs"]})
+                "program": PROGRAMS[args.program]})
     doc["created_first"] = args.first
-    doc["e2e"] = e2e_order(args, files, wins, ["off", "bcs"] if args.first == "off" else ["bcs", "off"])
+    doc["e2e"] = e2e_order(args, files, wins, ["off", args.program] if args.first == "off" else [args.program, "off"])
     RB.emit(doc, args)
 
 
@@ -161,6 +165,7 @@ def main():
     ap.add_argument("--commit", default=os.environ.get("COLOUR_BENCH_COMMIT", "unknown"))
     ap.add_argument("--e2e", action="store_true", help="the whole call from JPEG bytes through Pipeline.decode(..., colour=, colours=)")
     ap.add_argument("--first", choices=["off", "on"], default="off", help="--e2e: the pipeline created first")
+    ap.add_argument("--program", choices=[k for k in PROGRAMS if k != "empty"], default="bcs", help="--e2e: the program on every file")
     ap.add_argument("--cold", type=int, default=2, help="--e2e: uncounted calls per configuration")
     args = ap.parse_args()
     return e2e(args) if args.e2e else pixel_stage(args)
